@@ -7,9 +7,15 @@ the driver launches it under torch.distributed.run with one rank per GPU
 exactly K timed steps bracketed by barrier + torch.cuda.synchronize on both
 sides; elapsed is MAX over ranks; rank 0 prints ONE JSON line.
 
-Synthetic CIFAR-shaped data (no network for the real set), random-init
-weights, bf16 compute via the mi355x HIP kernels, full training step
-(zero_grad, fwd, loss, bwd, bucket all-reduce overlap, fused SGD step).
+A plain run does only that: setup, warmup, the timed steps, the optional
+`--dump-outputs DIR` (the last timed step's results as .npy, for comparing
+two builds on identical seeded inputs), the result line. Any measurement
+beyond the headline figure belongs behind `--full`.
+
+The inputs repeat exactly, and so do the outputs: every split reduction
+in the kernels (BN statistics, wgrads) stores per-block partials and folds
+them in a fixed order, so two runs of one build with the same arguments
+dump bit-identical arrays.
 """
 
 from __future__ import annotations
@@ -57,7 +63,61 @@ def parse_args():
                          "the graph's static-input copies are a net tax "
                          "(measured 109.9k eager vs 108.4k graphed at "
                          "b4096+)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, rank 0 writes what the last "
+                         "timed step computed as DIR/<name>.npy (float32): "
+                         "loss, logits, and the flat parameter and gradient "
+                         "buffers the step updated (a fixed seeded sample "
+                         "of the large ones, 64 MB at most in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beyond the headline "
+                         "figure (baselines, other configs, per-kernel "
+                         "figures). None exist yet, so today this changes "
+                         "nothing; later ones go behind it")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1 (ms_per_step is elapsed / steps)")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
+
+
+# --dump-outputs element caps: 2 x 7M + 1M fp32 values stay under 64 MB
+_DUMP_CAP = {"loss": 1, "logits": 1 << 20, "params": 7_000_000,
+             "grads": 7_000_000}
+
+
+N_POOL = 8  # synthetic batches, cycled: step i uses batch i % N_POOL
+
+
+def synthetic_pool(batch, size, num_classes, rank=0):
+    """The benchmark's inputs: N_POOL (images, labels) batches on the CPU,
+    from one generator seeded by the rank alone, so they are the same in
+    every run with the same arguments."""
+    g = torch.Generator(device="cpu").manual_seed(4321 + rank)
+    xs = [torch.randn(batch, 3, size, size, generator=g)
+          for _ in range(N_POOL)]
+    ys = [torch.randint(0, num_classes, (batch,), generator=g)
+          for _ in range(N_POOL)]
+    return xs, ys
+
+
+def dump_outputs(dirname, tensors):
+    """Write each tensor as <dirname>/<name>.npy in float32. Tensors larger
+    than their cap are sampled at fixed seeded flat indices (sorted), so two
+    builds run with the same arguments dump the same elements."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in tensors.items():
+        flat = t.detach().reshape(-1)
+        cap = _DUMP_CAP[name]
+        if flat.numel() > cap:
+            g = torch.Generator(device="cpu").manual_seed(97)
+            idx = torch.randperm(flat.numel(), generator=g)[:cap].sort().values
+            arr = flat[idx.to(flat.device)].float().cpu().numpy()
+        else:
+            arr = t.detach().float().cpu().numpy()
+        np.save(os.path.join(dirname, name + ".npy"), arr)
 
 
 def main():
@@ -128,16 +188,20 @@ def main():
                           grad_scale=gscale / loss_scale)
 
     # synthetic on-device data pool (new batch each step, cycling)
-    g = torch.Generator(device="cpu").manual_seed(4321 + rank)
-    n_pool = 8
-    pool_x = [torch.randn(args.batch, 3, args.size, args.size, generator=g)
-              .to(device) for _ in range(n_pool)]
-    pool_y = [torch.randint(0, num_classes, (args.batch,), generator=g)
-              .to(device) for _ in range(n_pool)]
+    n_pool = N_POOL
+    pool_x, pool_y = synthetic_pool(args.batch, args.size, num_classes, rank)
+    pool_x = [t.to(device) for t in pool_x]
+    pool_y = [t.to(device) for t in pool_y]
+
+    # --dump-outputs: the step leaves its logits here (graphed runs: the
+    # static tensor the replay writes)
+    kept = {} if args.dump_outputs else None
 
     def run_step(x, y):
         optimizer.zero_grad()
         out = net(x)
+        if kept is not None:
+            kept["logits"] = out
         loss = cross_entropy(out, y)
         if scaler is not None:
             used = scaler.scale_value  # capture: step_ok may grow it
@@ -207,6 +271,11 @@ def main():
         import torch.distributed as dist
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {
+            "loss": loss, "logits": kept["logits"],
+            "params": flat.flat_param, "grads": flat.flat_grad})
 
     n_gpus = world if use_cuda else 0
     global_batch = args.batch * world

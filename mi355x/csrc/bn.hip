@@ -5,15 +5,15 @@
 //  - bn_bwd_reduce: per-channel (sum dy*xhat, sum dy);
 //  - bn_bwd_dx: dx from the reduced terms.
 // Channel-minor layout makes every access coalesced along C; reductions are
-// per-thread private over an M-chunk, then one atomicAdd per channel per
-// chunk (guide Guideline 12).
+// per-thread private over an M-chunk, then one partial [2,C] row per chunk,
+// folded in a fixed order (fold_rows) so results repeat bit for bit.
 #include "common.h"
 
 namespace {
 
 template <typename T16>
 __global__ void bn_stats_kernel(const T16* __restrict__ x,
-                                float* __restrict__ out,  // [2,C]
+                                float* __restrict__ out,  // [chunks][2,C]
                                 long M, int C, long m_per_chunk) {
   const int c = blockIdx.y * blockDim.x + threadIdx.x;
   if (c >= C) return;
@@ -25,13 +25,9 @@ __global__ void bn_stats_kernel(const T16* __restrict__ x,
     s += v;
     ss += v * v;
   }
-  if (gridDim.x == 1) {
-    out[c] = s;
-    out[C + c] = ss;
-  } else {
-    atomicAdd(out + c, s);
-    atomicAdd(out + C + c, ss);
-  }
+  float* o = out + (long)blockIdx.x * 2 * C;  // own partial row
+  o[c] = s;
+  o[C + c] = ss;
 }
 
 template <typename T16>
@@ -63,7 +59,7 @@ __global__ void bn_bwd_reduce_kernel(const T16* __restrict__ x,
                                      const T16* __restrict__ y,
                                      const float* __restrict__ mean,
                                      const float* __restrict__ invstd,
-                                     float* __restrict__ out,  // [2,C]
+                                     float* __restrict__ out,  // [chunks][2,C]
                                      long M, int C, long m_per_chunk) {
   const int c = blockIdx.y * blockDim.x + threadIdx.x;
   if (c >= C) return;
@@ -78,13 +74,9 @@ __global__ void bn_bwd_reduce_kernel(const T16* __restrict__ x,
     s_dyx += d * xh;
     s_dy += d;
   }
-  if (gridDim.x == 1) {
-    out[c] = s_dyx;
-    out[C + c] = s_dy;
-  } else {
-    atomicAdd(out + c, s_dyx);
-    atomicAdd(out + C + c, s_dy);
-  }
+  float* o = out + (long)blockIdx.x * 2 * C;  // own partial row
+  o[c] = s_dyx;
+  o[C + c] = s_dy;
 }
 
 // y != null: mask dy by y>0 inline; dres != null: also emit the masked dy
@@ -121,7 +113,7 @@ __global__ void bn_bwd_dx_kernel(const T16* __restrict__ x,
 // every thread active); each thread owns a FIXED 8-channel group (c0 =
 // (tid*8) % C, invariant because 2048 % C == 0), accumulates 8 partial
 // pairs in registers, combines within the block through an LDS f32
-// accumulator, then one global atomicAdd per channel per block.
+// accumulator, then one partial [2,C] row per block (folded by fold_rows).
 // BWD=false: (sum x, sum x^2). BWD=true: (sum dy*xhat, sum dy), with the
 // fused ReLU mask from y when given.
 // asc/ash (BWD only, nullable): recompute the ReLU mask as
@@ -133,9 +125,9 @@ __global__ __launch_bounds__(256) void bn_reduce_fast(
     const unsigned char* __restrict__ msk, const float* __restrict__ mean,
     const float* __restrict__ invstd,
     const float* __restrict__ asc, const float* __restrict__ ash,
-    float* __restrict__ out,  // [2,C]
+    float* __restrict__ out,  // [blocks][2,C] partial rows
     long E, int C, long e_per_block) {
-  extern __shared__ __attribute__((aligned(16))) float lsum[];  // [2*C]
+  extern __shared__ __attribute__((aligned(16))) float lsum[];  // [rows][2*C]
   const int tid = threadIdx.x;
   const int c0 = (tid * 8) % C;
   float s0[8] = {}, s1[8] = {};
@@ -205,21 +197,28 @@ __global__ __launch_bounds__(256) void bn_reduce_fast(
     }
   }
   const bool leader = (threadIdx.x & 63) < gstride || gstride >= 64;
-  for (int c = tid; c < 2 * C; c += 256) lsum[c] = 0.f;
-  __syncthreads();
-  if (leader) {
+  // the leaders of one wave own distinct channel groups (c0 = 8*lane for
+  // C <= 512; beyond that the 4 waves split the channels between them),
+  // so each wave stores its sums into a row of its own — waves that share
+  // channels take different rows — and the rows are added in a fixed
+  // order: no LDS or global float atomics, the result repeats bit for bit
+  const int wpr = C > 512 ? C / 512 : 1;  // waves that tile one row
+  const int rows = 4 / wpr;               // see bn_reduce_lds
+  const int row = (tid >> 6) / wpr;
+  if (leader) {  // between them the leaders write every [row][2*C] slot
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
-      atomicAdd(lsum + c0 + u, s0[u]);
-      atomicAdd(lsum + C + c0 + u, s1[u]);
+      lsum[row * 2 * C + c0 + u] = s0[u];
+      lsum[row * 2 * C + C + c0 + u] = s1[u];
     }
   }
   __syncthreads();
-  for (int c = tid; c < 2 * C; c += 256)
-    if (gridDim.x == 1)
-      out[c] = lsum[c];
-    else
-      atomicAdd(out + c, lsum[c]);
+  float* o = out + (long)blockIdx.x * 2 * C;  // own partial row
+  for (int c = tid; c < 2 * C; c += 256) {
+    float a = lsum[c];
+    for (int r = 1; r < rows; ++r) a += lsum[r * 2 * C + c];
+    o[c] = a;
+  }
 }
 
 // vectorized elementwise BN apply / backward-dx: 16 B/lane linear sweep,
@@ -345,6 +344,25 @@ inline bool bn_fast_ok(long M, int C) {
   return C % 8 == 0 && 2048 % C == 0;
 }
 
+// LDS bytes bn_reduce_fast needs: one [2*C] row per wave sharing channels
+inline size_t bn_reduce_lds(int C) {
+  const int rows = C > 512 ? 4 / (C / 512) : 4;
+  return sizeof(float) * rows * 2 * C;
+}
+
+// output of a split reduction: the kernel writes grid.x partial rows of
+// [2,C]; one row is the result itself, more are folded in a fixed order
+inline at::Tensor bn_partial_rows(const at::Tensor& x, unsigned nrows, int C) {
+  return at::empty({(long)nrows, 2, C}, x.options().dtype(at::kFloat));
+}
+
+inline at::Tensor bn_fold(at::Tensor part, unsigned nrows, int C) {
+  if (nrows == 1) return part.view({2, C});
+  auto out = at::empty({2, C}, part.options());
+  fold_rows(part, out, 2L * C, nrows);
+  return out;
+}
+
 inline dim3 bn_fast_grid(long E, long& e_per_block) {
   static const long cap = [] {  // ablation knob
     const char* e = getenv("MI355X_BN_BLOCKS");
@@ -398,27 +416,25 @@ at::Tensor bn_stats(at::Tensor x) {
     const long E = M * (long)C;
     long e_per_block;
     dim3 grid = bn_fast_grid(E, e_per_block);
-    auto out = grid.x == 1 ? at::empty({2, C}, x.options().dtype(at::kFloat))
-                           : at::zeros({2, C}, x.options().dtype(at::kFloat));
+    auto out = bn_partial_rows(x, grid.x, C);
     DISPATCH_16(x, T16, {
       hipLaunchKernelGGL((bn_reduce_fast<T16, false>), grid, dim3(256),
-                         2 * C * sizeof(float), cur_stream(),
+                         bn_reduce_lds(C), cur_stream(),
                          (const T16*)x.data_ptr(), nullptr, nullptr, nullptr,
                          nullptr, nullptr, nullptr, out.data_ptr<float>(), E,
                          C, e_per_block);
     });
-    return out;
+    return bn_fold(out, grid.x, C);
   }
   long m_per_chunk;
   dim3 grid = chan_grid(M, C, m_per_chunk);
-  auto out = grid.x == 1 ? at::empty({2, C}, x.options().dtype(at::kFloat))
-                         : at::zeros({2, C}, x.options().dtype(at::kFloat));
+  auto out = bn_partial_rows(x, grid.x, C);
   DISPATCH_16(x, T16, {
     hipLaunchKernelGGL(bn_stats_kernel<T16>, grid, dim3(256), 0, cur_stream(),
                        (const T16*)x.data_ptr(), out.data_ptr<float>(), M, C,
                        m_per_chunk);
   });
-  return out;
+  return bn_fold(out, grid.x, C);
 }
 
 // returns {y, mask}: mask is a 1-bit-per-element "y > 0" map (u8, one
@@ -483,13 +499,12 @@ at::Tensor bn_bwd_reduce(at::Tensor x, at::Tensor dy, at::Tensor y,
     const long E = M * (long)C;
     long e_per_block;
     dim3 grid = bn_fast_grid(E, e_per_block);
-    auto out = grid.x == 1 ? at::empty({2, C}, x.options().dtype(at::kFloat))
-                           : at::zeros({2, C}, x.options().dtype(at::kFloat));
+    auto out = bn_partial_rows(x, grid.x, C);
     const bool rc = asc.defined() && asc.numel() > 0;
     DISPATCH_16(x, T16, {
       if (rc)
         hipLaunchKernelGGL((bn_reduce_fast<T16, true, true>), grid,
-                           dim3(256), 2 * C * sizeof(float), cur_stream(),
+                           dim3(256), bn_reduce_lds(C), cur_stream(),
                            (const T16*)x.data_ptr(),
                            (const T16*)dy.data_ptr(), nullptr,
                            mean.data_ptr<float>(), invstd.data_ptr<float>(),
@@ -497,7 +512,7 @@ at::Tensor bn_bwd_reduce(at::Tensor x, at::Tensor dy, at::Tensor y,
                            out.data_ptr<float>(), E, C, e_per_block);
       else
         hipLaunchKernelGGL((bn_reduce_fast<T16, true>), grid, dim3(256),
-                           2 * C * sizeof(float), cur_stream(),
+                           bn_reduce_lds(C), cur_stream(),
                            (const T16*)x.data_ptr(),
                            (const T16*)dy.data_ptr(),
                            mask.numel() ? mask.data_ptr<unsigned char>()
@@ -506,12 +521,11 @@ at::Tensor bn_bwd_reduce(at::Tensor x, at::Tensor dy, at::Tensor y,
                            nullptr, nullptr,
                            out.data_ptr<float>(), E, C, e_per_block);
     });
-    return out;
+    return bn_fold(out, grid.x, C);
   }
   long m_per_chunk;
   dim3 grid = chan_grid(M, C, m_per_chunk);
-  auto out = grid.x == 1 ? at::empty({2, C}, x.options().dtype(at::kFloat))
-                         : at::zeros({2, C}, x.options().dtype(at::kFloat));
+  auto out = bn_partial_rows(x, grid.x, C);
   DISPATCH_16(x, T16, {
     hipLaunchKernelGGL(bn_bwd_reduce_kernel<T16>, grid, dim3(256), 0,
                        cur_stream(), (const T16*)x.data_ptr(),
@@ -521,7 +535,7 @@ at::Tensor bn_bwd_reduce(at::Tensor x, at::Tensor dy, at::Tensor y,
                        invstd.data_ptr<float>(), out.data_ptr<float>(), M, C,
                        m_per_chunk);
   });
-  return out;
+  return bn_fold(out, grid.x, C);
 }
 
 std::vector<at::Tensor> bn_bwd_dx(at::Tensor x, at::Tensor dy, at::Tensor y,

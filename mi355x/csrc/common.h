@@ -75,3 +75,54 @@ DEV_INLINE short f32_to_s16(float f) {
 static inline hipStream_t cur_stream() {
   return (hipStream_t)at::cuda::getCurrentCUDAStream().stream();
 }
+
+// out[e] = sum_z part[z][e], always added in the same order, so split
+// reductions that store per-block partial rows and fold them here give
+// bit-identical results from run to run (float atomicAdd onto the output
+// does not: the order the blocks arrive in varies). A block covers 32
+// elements x 32 interleaved z-slices (few dependent loads per thread: the
+// fold is latency-bound); the slices meet in LDS.
+static __global__ __launch_bounds__(1024) void fold_rows_kernel(
+    const float* __restrict__ part, float* __restrict__ out, long E, int nz) {
+  __shared__ float l[32][32];
+  const int le = threadIdx.x & 31, sl = threadIdx.x >> 5;
+  const long e = (long)blockIdx.x * 32 + le;
+  float a = 0.f;
+  if (e < E) {
+#pragma unroll 8
+    for (int z = sl; z < nz; z += 32) a += part[(long)z * E + e];
+  }
+  l[sl][le] = a;
+  __syncthreads();
+  if (sl == 0 && e < E) {
+    float s = l[0][le];
+#pragma unroll
+    for (int j = 1; j < 32; ++j) s += l[j][le];
+    out[e] = s;
+  }
+}
+
+// the same fold for a few rows (split-M wgrads of large filters: nz of
+// 2..8 over up to millions of elements): one element per thread, every
+// lane busy, rows added in order
+static __global__ __launch_bounds__(256) void fold_few_rows_kernel(
+    const float* __restrict__ part, float* __restrict__ out, long E, int nz) {
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= E) return;
+  float a = part[e];
+  for (int z = 1; z < nz; ++z) a += part[(long)z * E + e];
+  out[e] = a;
+}
+
+static inline void fold_rows(const at::Tensor& part, at::Tensor& out, long E,
+                             long nz) {
+  if (nz <= 8) {
+    hipLaunchKernelGGL(fold_few_rows_kernel, dim3((unsigned)cdiv_l(E, 256)),
+                       dim3(256), 0, cur_stream(), part.data_ptr<float>(),
+                       out.data_ptr<float>(), E, (int)nz);
+    return;
+  }
+  hipLaunchKernelGGL(fold_rows_kernel, dim3((unsigned)cdiv_l(E, 32)),
+                     dim3(1024), 0, cur_stream(), part.data_ptr<float>(),
+                     out.data_ptr<float>(), E, (int)nz);
+}

@@ -121,7 +121,6 @@ __global__ void conv_wgrad_direct(const T16* __restrict__ x,
   const long M = (long)N * P * Q;
   const long m0 = (long)blockIdx.y * m_per_chunk;
   const long m1 = min(M, m0 + m_per_chunk);
-  const int nchunks = gridDim.y;
   for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < total_w;
        t += (long)gridDim.x * blockDim.x) {
     const int c = (int)(t % C);
@@ -149,11 +148,9 @@ __global__ void conv_wgrad_direct(const T16* __restrict__ x,
       }
     }
     // store in the parameter layout [K,C,R,S]
-    float* out = dw + ((long)k * C + c) * ((long)R * S) + (long)r * S + s;
-    if (nchunks == 1)
-      *out = acc;
-    else
-      atomicAdd(out, acc);
+    // (split-M: one partial filter per chunk, folded in order by fold_rows)
+    dw[(long)blockIdx.y * total_w + ((long)k * C + c) * ((long)R * S) +
+       (long)r * S + s] = acc;
   }
 }
 
@@ -1002,7 +999,8 @@ std::vector<at::Tensor> conv2d_fwd_stats(at::Tensor x, at::Tensor w,
   const int R = w.size(1), S = w.size(2);
   const int P = out_dim(H, R, stride, pad), Q = out_dim(W, S, stride, pad);
   auto y = at::empty({N, P, Q, K}, x.options());
-  auto stats = at::zeros({2, K}, x.options().dtype(at::kFloat));
+  // empty, not zeros: the ordered slab fold stores every stats element
+  auto stats = at::empty({2, K}, x.options().dtype(at::kFloat));
   auto empty_bias = at::empty(0, x.options().dtype(at::kFloat));
   conv_fwd_mfma_launch(x, w, empty_bias, y, stride, pad, 0, stats,
                        at::Tensor(), at::Tensor());
@@ -1032,7 +1030,7 @@ std::vector<at::Tensor> conv2d_fwd_scaled(at::Tensor x, at::Tensor w,
   const int P = out_dim(H, R, stride, pad), Q = out_dim(W_, S, stride, pad);
   auto y = at::empty({N, P, Q, K}, x.options());
   auto stats = want_stats
-                   ? at::zeros({2, K}, x.options().dtype(at::kFloat))
+                   ? at::empty({2, K}, x.options().dtype(at::kFloat))
                    : at::Tensor();
   auto empty_bias = at::empty(0, x.options().dtype(at::kFloat));
   conv_fwd_mfma_launch(x, w, empty_bias, y, stride, pad, 0, stats, asc, ash);
@@ -1204,17 +1202,18 @@ at::Tensor conv2d_wgrad(at::Tensor x, at::Tensor dy, long R, long S,
                                     std::max<long>(1, (256L * 8192) / std::max(total_w, 1L)));
   nchunks = std::max(nchunks, 1);
   const long m_per_chunk = cdiv_l(M, nchunks);
-  auto dw = nchunks == 1
-                ? at::empty({K, (long)C, R, S},
-                            x.options().dtype(at::kFloat))
-                : at::zeros({K, (long)C, R, S}, x.options().dtype(at::kFloat));
+  auto dw = at::empty({K, (long)C, R, S}, x.options().dtype(at::kFloat));
+  auto part = nchunks == 1
+                  ? dw
+                  : at::empty({nchunks, total_w}, x.options().dtype(at::kFloat));
   dim3 grid((unsigned)std::min<long>(cdiv_l(total_w, 256), 4096), nchunks);
   DISPATCH_16(x, T16, {
     hipLaunchKernelGGL(conv_wgrad_direct<T16>, grid, dim3(256), 0,
                        cur_stream(), (const T16*)x.data_ptr(),
-                       (const T16*)dy.data_ptr(), dw.data_ptr<float>(), N, H,
-                       W, C, K, (int)R, (int)S, P, Q, (int)stride, (int)pad,
+                       (const T16*)dy.data_ptr(), part.data_ptr<float>(), N,
+                       H, W, C, K, (int)R, (int)S, P, Q, (int)stride, (int)pad,
                        m_per_chunk);
   });
+  if (nchunks > 1) fold_rows(part, dw, total_w, nchunks);
   return dw;
 }

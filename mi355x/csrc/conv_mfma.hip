@@ -358,8 +358,9 @@ __global__ void conv_stats_partial(const float* __restrict__ slab,
   out[((long)by * gridDim.x + blockIdx.x) * bnt2 + t] = acc;
 }
 
-// stats[2][C] = sum over gx of slab[gy][gx][2][BNT]; one block per
-// (by, gx-slice), coalesced loads, few global atomics
+// stats[2][C] = sum over gx of slab[gy][gx][2][BNT]; one block per by
+// sums the (at most 64) remaining rows in order — plain stores, so the
+// statistics repeat bit for bit (no float atomics)
 __global__ void conv_stats_reduce(const float* __restrict__ slab,
                                   float* __restrict__ stats, int gx, int bnt2,
                                   int C, int bx_per_block) {
@@ -374,10 +375,7 @@ __global__ void conv_stats_reduce(const float* __restrict__ slab,
   const int bnt = bnt2 / 2;
   const int h = t / bnt;
   const int c = by * bnt + (t % bnt);
-  if (gridDim.x == 1)
-    stats[h * C + c] = acc;
-  else
-    atomicAdd(stats + h * C + c, acc);
+  stats[h * C + c] = acc;  // launched with gridDim.x == 1
 }
 
 // stride-2 dgrad, parity-specialized: dx positions partition by
@@ -547,7 +545,8 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad_s2_gemm(
 
 }  // namespace
 
-// fold slab [by][gx][bnt2] -> stats[2,C]; two-level when gx is large
+// fold slab [by][gx][bnt2] -> stats[2,C]; partial levels (plain sums into
+// fewer rows) until at most 64 rows are left for the single final block
 // (external linkage: the stem kernels reuse it)
 void stats_slab_reduce(at::Tensor slab, at::Tensor stats, int gx, int bnt2,
                        int C) {
@@ -562,11 +561,19 @@ void stats_slab_reduce(at::Tensor slab, at::Tensor stats, int gx, int bnt2,
     slab = l2;
     gx = gx2;
   }
-  const int bpb = (int)cdiv_l(gx, 64);
-  dim3 rgrid((unsigned)cdiv_l(gx, bpb), by);
-  hipLaunchKernelGGL(conv_stats_reduce, rgrid, dim3(256), 0, cur_stream(),
-                     slab.data_ptr<float>(), stats.data_ptr<float>(), gx,
-                     bnt2, C, bpb);
+  if (gx > 64) {
+    const int bpb2 = (int)cdiv_l(gx, 64);
+    const int gx3 = (int)cdiv_l(gx, bpb2);
+    auto l3 = at::empty({(long)by * gx3 * bnt2}, slab.options());
+    hipLaunchKernelGGL(conv_stats_partial, dim3(gx3, by), dim3(256), 0,
+                       cur_stream(), slab.data_ptr<float>(),
+                       l3.data_ptr<float>(), gx, bnt2, bpb2);
+    slab = l3;
+    gx = gx3;
+  }
+  hipLaunchKernelGGL(conv_stats_reduce, dim3(1, by), dim3(256), 0,
+                     cur_stream(), slab.data_ptr<float>(),
+                     stats.data_ptr<float>(), gx, bnt2, C, gx);
 }
 
 // ---------------------------------------------------------------------------
@@ -2009,7 +2016,7 @@ void conv_fwd_mfma_genc_launch(at::Tensor x, at::Tensor wpad, at::Tensor bias,
 }
 
 // fwd: in = x[N,Hi,Wi,CI], wgt = w16 [KO, R,S,CI] row-major.
-// stats (optional, zeroed [2,C]): conv->BN fusion — the epilogue emits
+// stats (optional, [2,C], fully overwritten): conv->BN fusion — the epilogue emits
 // per-block (sum,sumsq) partials to a slab and conv_stats_reduce folds
 // them, replacing BN's separate full-tensor bn_stats pass.
 // asc/ash (optional [CI] fp32): lazy-BN A-side transform — the x operand

@@ -58,8 +58,9 @@ __global__ void linear_dgrad_kernel(const T16* __restrict__ dy,
   }
 }
 
-// dw[N,K] (f32) = dy[M,N]^T @ x[M,K]; split-M over blockIdx.y with
-// atomics (classifier dw is small, the M loop is the long axis)
+// dw[N,K] (f32) = dy[M,N]^T @ x[M,K]; split-M over blockIdx.y, one
+// partial [N,K] row per chunk folded in a fixed order by fold_rows
+// (classifier dw is small, the M loop is the long axis)
 template <typename T16>
 __global__ void linear_wgrad_kernel(const T16* __restrict__ x,
                                     const T16* __restrict__ dy,
@@ -76,10 +77,7 @@ __global__ void linear_wgrad_kernel(const T16* __restrict__ x,
     for (int m = m0; m < m1; ++m)
       acc += F16<T16>::to_f32(dy[(long)m * N + nn]) *
              F16<T16>::to_f32(x[(long)m * K + k]);
-    if (gridDim.y == 1)
-      dw[t] = acc;
-    else
-      atomicAdd(dw + t, acc);
+    dw[(long)blockIdx.y * total + t] = acc;
   }
 }
 
@@ -151,14 +149,17 @@ at::Tensor linear_wgrad(at::Tensor x, at::Tensor dy) {
                                     cdiv_l(M, 64));
   const int m_per_chunk = (int)cdiv_l(M, nchunks);
   nchunks = (int)cdiv_l(M, m_per_chunk);
-  auto dw = nchunks == 1 ? at::empty({N, K}, x.options().dtype(at::kFloat))
-                         : at::zeros({N, K}, x.options().dtype(at::kFloat));
+  auto dw = at::empty({N, K}, x.options().dtype(at::kFloat));
+  auto part = nchunks == 1
+                  ? dw
+                  : at::empty({nchunks, N, K}, x.options().dtype(at::kFloat));
   dim3 grid((unsigned)std::min<long>(xy_blocks, 4096), nchunks);
   DISPATCH_16(x, T16, {
     hipLaunchKernelGGL(linear_wgrad_kernel<T16>, grid, dim3(256), 0,
                        cur_stream(), (const T16*)x.data_ptr(),
-                       (const T16*)dy.data_ptr(), dw.data_ptr<float>(), M, N,
-                       K, m_per_chunk);
+                       (const T16*)dy.data_ptr(), part.data_ptr<float>(), M,
+                       N, K, m_per_chunk);
   });
+  if (nchunks > 1) fold_rows(part, dw, total, nchunks);
   return dw;
 }

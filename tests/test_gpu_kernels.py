@@ -174,6 +174,53 @@ def test_batch_norm_train_fwd_bwd(shape, res, act):
         _close(resg.grad, resc.grad)
 
 
+@pytest.mark.parametrize("C,M", [
+    (8, 700),      # 1 leader lane per wave; 3 blocks, ragged last (few-rows fold)
+    (6, 3000),     # channel-chunk fallback kernels (2048 % C != 0), 3 chunks
+    (64, 5000),    # 157 blocks: 32-slice fold
+    (512, 37),     # 4 LDS rows, every lane a leader; 10 blocks, ragged last
+    (1024, 37),    # 2 LDS rows (waves 0/1 and 2/3 tile the channels)
+    (2048, 701),   # 1 LDS row; block cap: 351 blocks of 2 sweeps, ragged last
+])
+def test_bn_reductions_split_and_fold(C, M):
+    """bn_stats and bn_bwd_reduce alone, at every LDS-row layout of
+    bn_reduce_fast and with more than one partial row to fold, against
+    float64 sums of the same bf16 values. Bound: the worst case of fp32
+    summation in ANY order, (n + 4) * 2^-24 * sum|term| per channel (n
+    terms, +4 for the roundings inside a term); and a second call returns
+    the same bits."""
+    from mi355x.ops._ext import ext
+    g = torch.Generator().manual_seed(11)
+    x = (torch.randn(M, C, generator=g) * 2 + 0.5).to(torch.bfloat16).cuda()
+    dy = torch.randn(M, C, generator=g).to(torch.bfloat16).cuda()
+    mean = torch.randn(C, generator=g).cuda()
+    invstd = (torch.rand(C, generator=g) + 0.5).cuda()
+    ef = torch.empty(0, device="cuda")
+    e16 = torch.empty(0, device="cuda", dtype=torch.bfloat16)
+    e8 = torch.empty(0, device="cuda", dtype=torch.uint8)
+
+    def bound(terms):
+        return (M + 4) * 2.0 ** -24 * terms.abs().sum(0)
+
+    s = ext().bn_stats(x)
+    assert s.shape == (2, C)
+    xd = x.double().cpu()
+    for got, terms in ((s[0], xd), (s[1], xd * xd)):
+        err = (got.double().cpu() - terms.sum(0)).abs()
+        assert (err <= bound(terms)).all(), (err / bound(terms)).max()
+    assert torch.equal(ext().bn_stats(x), s)
+
+    r = ext().bn_bwd_reduce(x, dy, e16, mean, invstd, e8, ef, ef)
+    assert r.shape == (2, C)
+    dd = dy.double().cpu()
+    xh = (xd - mean.double().cpu()) * invstd.double().cpu()
+    for got, terms in ((r[0], dd * xh), (r[1], dd)):
+        err = (got.double().cpu() - terms.sum(0)).abs()
+        assert (err <= bound(terms)).all(), (err / bound(terms)).max()
+    assert torch.equal(
+        ext().bn_bwd_reduce(x, dy, e16, mean, invstd, e8, ef, ef), r)
+
+
 def test_batch_norm_eval():
     C = 8
     xc, xg = _pair((2, 4, 4, C))
