@@ -135,7 +135,8 @@ def r50_fwd_steps():
 
 
 def convperf():
-    """fwd conv timing per layer shape (glds A/B via MI355X_CONV_GLDS)."""
+    """fwd conv timing per layer shape (patch vs per-tap gather A/B via
+    MI355X_CONV_PATCH)."""
     import time
     import mi355x.ops as O
     shapes = [  # (N,H,W,C,K,ksz,stride,pad) — r18-CIFAR b1024 layers

@@ -364,10 +364,8 @@ inline at::Tensor bn_fold(at::Tensor part, unsigned nrows, int C) {
 }
 
 inline dim3 bn_fast_grid(long E, long& e_per_block) {
-  static const long cap = [] {  // ablation knob
-    const char* e = getenv("MI355X_BN_BLOCKS");
-    return e ? atol(e) : 512L;  // A/B: 512 blocks 3.4/5.0 TB/s vs 1024 2.9/4.5
-  }();
+  // ablation knob. A/B: 512 blocks 3.4/5.0 TB/s vs 1024 2.9/4.5
+  static const long cap = EnvKnob("MI355X_BN_BLOCKS").num(512);
   long blocks = std::min<long>(cdiv_l(E, 2048), cap);
   e_per_block = cdiv_l(cdiv_l(E, blocks), 2048) * 2048;
   blocks = cdiv_l(E, e_per_block);

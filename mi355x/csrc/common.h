@@ -76,6 +76,49 @@ static inline hipStream_t cur_stream() {
   return (hipStream_t)at::cuda::getCurrentCUDAStream().stream();
 }
 
+// Launch `kern` with 256 threads on the current stream. Each argument is
+// converted to the kernel's parameter type, as in a plain call.
+template <typename... P, typename... A>
+static inline void launch256(void (*kern)(P...), dim3 grid, size_t lds_bytes,
+                             A&&... args) {
+  hipLaunchKernelGGL(kern, grid, dim3(256), lds_bytes, cur_stream(),
+                     static_cast<P>(args)...);
+}
+
+// Runtime value -> template argument: calls f(std::integral_constant<.., V>)
+// for the V in Vs that equals v, so a launcher names its kernel once and the
+// listed values are exactly the variants that get instantiated.
+//   pick<4, 2>(nt, [&](auto NT) { launch256(kern<T16, NT>, ...); });
+template <auto... Vs, typename T, typename F>
+static inline void pick(T v, F&& f) {
+  const bool hit =
+      ((v == Vs ? (f(std::integral_constant<decltype(Vs), Vs>{}), true)
+                : false) || ...);
+  TORCH_CHECK(hit, "pick: no kernel variant for this value");
+}
+
+// The library's environment knobs (MI355X_*, listed in the README) all go
+// through this reader. Keep the result in a function-local static: a knob
+// is read once per process, never per launch.
+struct EnvKnob {
+  const char* val;
+  explicit EnvKnob(const char* name) : val(getenv(name)) {}
+  // on/off knob that defaults to on: only a leading '0' turns it off
+  bool on() const { return !val || val[0] != '0'; }
+  long num(long dflt) const { return val ? atol(val) : dflt; }
+};
+
+// Split `total` items into about `want` chunks of equal size, a multiple of
+// `granule`: {items per chunk, chunks actually needed}.
+struct SplitPlan {
+  long per, n;
+};
+static inline SplitPlan split_plan(long total, long want, long granule = 1) {
+  const long per =
+      cdiv_l(cdiv_l(total, std::max<long>(want, 1)), granule) * granule;
+  return {per, cdiv_l(total, per)};
+}
+
 // out[e] = sum_z part[z][e], always added in the same order, so split
 // reductions that store per-block partial rows and fold them here give
 // bit-identical results from run to run (float atomicAdd onto the output

@@ -12,7 +12,7 @@
 //    accumulation. These replaced the register-window variants for those
 //    shapes after PMC showed them latency-bound (profiles/).
 // The MFMA implicit-GEMM path (conv_mfma.hip) takes every C%64==0 shape.
-#include "common.h"
+#include "conv_internal.h"
 
 namespace {
 
@@ -310,6 +310,93 @@ __device__ __forceinline__ typename Dot2<T16>::v2 pack2(T16 a, T16 b) {
   return r;
 }
 
+// ---- LDS strip shared by the stem kernels and their launchers -----------
+// A strip holds the input rows under one output row: `rows` rows of
+// `selems` elements. +4: 8B-aligned row stride with >=1 zeroed pad element
+// (the 7x7 fwd's pair 10 reads element 6q+21, one past the last tap).
+struct StripGeom {
+  int sstride;  // row stride, elements
+  int bytes;    // whole strip
+};
+__host__ __device__ inline StripGeom strip_geom(int rows, int selems,
+                                                int elem_bytes) {
+  const int sstride = (selems + 4) & ~3;
+  return {sstride, rows * sstride * elem_bytes};
+}
+__host__ __device__ inline StripGeom stem7_strip(int Wo, int elem_bytes) {
+  return strip_geom(7, (2 * Wo + 5) * 3, elem_bytes);
+}
+__host__ __device__ inline StripGeom stem3_strip(int Wo) {
+  return strip_geom(3, (Wo + 2) * 3, 4);
+}
+
+template <typename D, typename T16>
+DEV_INLINE D strip_cvt(T16 v) {
+  if constexpr (std::is_same<D, float>::value)
+    return F16<T16>::to_f32(v);
+  else
+    return v;
+}
+
+// Cooperative strip fill (256 threads): rows ih0 .. ih0+ROWS-1 of image n,
+// kept as D = T16 or converted once to D = float. Strip element
+// (iw+pad)*3+c maps to the CONTIGUOUS x row element iw*3+c, so the
+// interior is short8 block copies (the elementwise /3-decode version was
+// ~19 serial 2B loads per thread); pads and invalid rows are zeroed.
+// off3 = 3*pad strip elements precede the payload. With D = T16 the short8
+// store lands on a 2-byte-aligned LDS address when off3 is odd: only the
+// 7x7 fwd stem uses that form.
+template <int ROWS, typename D, typename T16>
+DEV_INLINE void strip_fill(D* xs, const T16* x, int n, int H, int W, int ih0,
+                           int off3, int sstride) {
+  const D z{};
+  const int row3 = 3 * W;  // contiguous payload per row
+  const int nv8 = (row3 + 7) / 8;
+  for (int t = threadIdx.x; t < ROWS * nv8; t += 256) {
+    const int rr = t / nv8;
+    const int j8 = (t - rr * nv8) * 8;
+    const int ih = ih0 + rr;
+    D* dst = xs + (long)rr * sstride + off3 + j8;
+    if ((row3 & 7) == 0 && (unsigned)ih < (unsigned)H && j8 + 8 <= row3) {
+      const short8 v = *reinterpret_cast<const short8*>(
+          x + ((long)n * H + ih) * row3 + j8);
+      if constexpr (std::is_same<D, float>::value) {
+#pragma unroll
+        for (int u = 0; u < 8; ++u) dst[u] = s16_to_f32<T16>(v[u]);
+      } else {
+        *reinterpret_cast<short8*>(dst) = v;
+      }
+    } else {
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int e = j8 + u;
+        dst[u] = (e < row3 && (unsigned)ih < (unsigned)H)
+                     ? strip_cvt<D>(x[((long)n * H + ih) * row3 + e])
+                     : z;
+      }
+    }
+  }
+  // zero the pad columns (and the alignment tail) of every row
+  for (int t = threadIdx.x; t < ROWS * (sstride - row3); t += 256) {
+    const int nz = sstride - row3;
+    const int rr = t / nz;
+    const int e = t - rr * nz;
+    xs[(long)rr * sstride + (e < off3 ? e : row3 + e)] = z;
+  }
+}
+
+// one dy output row (n elements, coalesced) into LDS for the stem wgrads
+template <typename T16>
+DEV_INLINE void stage_dy_row(T16* dys, const T16* dyrow, int n) {
+  if ((n & 7) == 0) {
+    for (int i = threadIdx.x * 8; i < n; i += 256 * 8)
+      *reinterpret_cast<short8*>(dys + i) =
+          *reinterpret_cast<const short8*>(dyrow + i);
+  } else {
+    for (int i = threadIdx.x; i < n; i += 256) dys[i] = dyrow[i];
+  }
+}
+
 // ---- 7x7/stride-2 stem fwd v3: cooperative LDS staging -----------------
 // v2 (register sliding window) measured latency-bound: each wave had ~1
 // cache line in flight, issued right before use. v3 stages the whole
@@ -328,48 +415,12 @@ __global__ __launch_bounds__(256) void conv_fwd_stem7_lds(
   constexpr int ROWS = 7, WPAIR = 11;
   extern __shared__ char smem[];
   T16* xs = reinterpret_cast<T16*>(smem);
-  const int selems = (2 * Wo + 5) * 3;          // strip elements per row
-  // +4: 8B-aligned row stride with >=1 zeroed pad element (pair 10's hi
-  // half reads element 6q+21, one past the last tap)
-  const int sstride = (selems + 4) & ~3;
+  const int sstride = stem7_strip(Wo, sizeof(T16)).sstride;
 
   const int p = blockIdx.x % Ho;
   const int n = blockIdx.x / Ho;
-  const int ih0 = 2 * p - pad;
-
-  // ---- cooperative strip fill. Strip element (iw+pad)*3+c maps to the
-  // CONTIGUOUS x row element iw*3+c, so the interior is short8 block
-  // copies (the elementwise /3-decode version was ~19 serial 2B loads
-  // per thread); pads and invalid rows are vector-zeroed.
   const T16 z{};
-  const int row3 = 3 * W;             // contiguous payload per row
-  const int off3 = 3 * pad;           // strip elements before the payload
-  const int nv8 = (row3 + 7) / 8;
-  for (int t = threadIdx.x; t < ROWS * nv8; t += 256) {
-    const int rr = t / nv8;
-    const int j8 = (t - rr * nv8) * 8;
-    const int ih = ih0 + rr;
-    T16* dst = xs + (long)rr * sstride + off3 + j8;
-    if ((row3 & 7) == 0 && (unsigned)ih < (unsigned)H && j8 + 8 <= row3) {
-      *reinterpret_cast<short8*>(dst) = *reinterpret_cast<const short8*>(
-          x + ((long)n * H + ih) * row3 + j8);
-    } else {
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const int e = j8 + u;
-        dst[u] = (e < row3 && (unsigned)ih < (unsigned)H)
-                     ? x[((long)n * H + ih) * row3 + e]
-                     : z;
-      }
-    }
-  }
-  // zero the pad columns (and the alignment tail) of every row
-  for (int t = threadIdx.x; t < ROWS * (sstride - row3); t += 256) {
-    const int nz = sstride - row3;
-    const int rr = t / nz;
-    const int e = t - rr * nz;
-    xs[(long)rr * sstride + (e < off3 ? e : row3 + e)] = z;
-  }
+  strip_fill<ROWS>(xs, x, n, H, W, 2 * p - pad, 3 * pad, sstride);
 
   const int k = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -422,43 +473,11 @@ __global__ __launch_bounds__(256) void conv_fwd_stem3_lds(
     int W, int K, int Ho, int Wo, long wrow_stride, int act, int has_bias) {
   extern __shared__ __attribute__((aligned(16))) char smem3[];
   float* xs = reinterpret_cast<float*>(smem3);
-  const int selems = (Wo + 2) * 3;
-  const int sstride = (selems + 4) & ~3;
+  const int sstride = stem3_strip(Wo).sstride;
 
   const int p = blockIdx.x % Ho;
   const int n = blockIdx.x / Ho;
-  {
-    // vectorized fill (see the 7x7 stem comment: strip interior is one
-    // contiguous x row)
-    const int row3 = 3 * W, off3 = 3;
-    const int nv8 = (row3 + 7) / 8;
-    for (int t = threadIdx.x; t < 3 * nv8; t += 256) {
-      const int rr = t / nv8;
-      const int j8 = (t - rr * nv8) * 8;
-      const int ih = p - 1 + rr;
-      float* dst = xs + (long)rr * sstride + off3 + j8;
-      if ((row3 & 7) == 0 && (unsigned)ih < (unsigned)H && j8 + 8 <= row3) {
-        const short8 v = *reinterpret_cast<const short8*>(
-            x + ((long)n * H + ih) * row3 + j8);
-#pragma unroll
-        for (int u = 0; u < 8; ++u) dst[u] = s16_to_f32<T16>(v[u]);
-      } else {
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          const int e = j8 + u;
-          dst[u] = (e < row3 && (unsigned)ih < (unsigned)H)
-                       ? F16<T16>::to_f32(x[((long)n * H + ih) * row3 + e])
-                       : 0.f;
-        }
-      }
-    }
-    for (int t = threadIdx.x; t < 3 * (sstride - row3); t += 256) {
-      const int nz = sstride - row3;
-      const int rr = t / nz;
-      const int e = t - rr * nz;
-      xs[(long)rr * sstride + (e < off3 ? e : row3 + e)] = 0.f;
-    }
-  }
+  strip_fill<3>(xs, x, n, H, W, p - 1, 3, sstride);
 
   const int k = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -493,10 +512,10 @@ __global__ __launch_bounds__(256) void conv_wgrad_stem3_lds(
     float* __restrict__ part,  // [gridDim.x*4][K*3*3*3]
     int N, int H, int W, int K, int Ho, int Wo, int rows_per_chunk) {
   extern __shared__ __attribute__((aligned(16))) char smem3[];
-  const int selems = (Wo + 2) * 3;
-  const int sstride = (selems + 4) & ~3;
+  const StripGeom sg = stem3_strip(Wo);
+  const int sstride = sg.sstride;
   float* xs = reinterpret_cast<float*>(smem3);
-  T16* dys = reinterpret_cast<T16*>(smem3 + 3 * sstride * 4);
+  T16* dys = reinterpret_cast<T16*>(smem3 + sg.bytes);
 
   const int k = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -512,45 +531,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_stem3_lds(
     const int p = (int)(row % Ho);
     const int n = (int)(row / Ho);
     __syncthreads();
-    {
-      const int row3 = 3 * W, off3 = 3;
-      const int nv8 = (row3 + 7) / 8;
-      for (int t = threadIdx.x; t < 3 * nv8; t += 256) {
-        const int rr = t / nv8;
-        const int j8 = (t - rr * nv8) * 8;
-        const int ih = p - 1 + rr;
-        float* dst = xs + (long)rr * sstride + off3 + j8;
-        if ((row3 & 7) == 0 && (unsigned)ih < (unsigned)H && j8 + 8 <= row3) {
-          const short8 v = *reinterpret_cast<const short8*>(
-              x + ((long)n * H + ih) * row3 + j8);
-#pragma unroll
-          for (int u = 0; u < 8; ++u) dst[u] = s16_to_f32<T16>(v[u]);
-        } else {
-#pragma unroll
-          for (int u = 0; u < 8; ++u) {
-            const int e = j8 + u;
-            dst[u] = (e < row3 && (unsigned)ih < (unsigned)H)
-                         ? F16<T16>::to_f32(
-                               x[((long)n * H + ih) * row3 + e])
-                         : 0.f;
-          }
-        }
-      }
-      for (int t = threadIdx.x; t < 3 * (sstride - row3); t += 256) {
-        const int nz = sstride - row3;
-        const int rr = t / nz;
-        const int e = t - rr * nz;
-        xs[(long)rr * sstride + (e < off3 ? e : row3 + e)] = 0.f;
-      }
-    }
-    const T16* dyrow = dy + row * Wo * K;
-    if (((Wo * K) & 7) == 0) {
-      for (int i = threadIdx.x * 8; i < Wo * K; i += 256 * 8)
-        *reinterpret_cast<short8*>(dys + i) =
-            *reinterpret_cast<const short8*>(dyrow + i);
-    } else {
-      for (int i = threadIdx.x; i < Wo * K; i += 256) dys[i] = dyrow[i];
-    }
+    strip_fill<3>(xs, x, n, H, W, p - 1, 3, sstride);
+    stage_dy_row(dys, dy + row * Wo * K, Wo * K);
     __syncthreads();
 
     for (int q = q0; q < q1; ++q) {
@@ -606,10 +588,10 @@ __global__ __launch_bounds__(256) void conv_wgrad_stem7_lds(
     int N, int H, int W, int K, int Ho, int Wo, int pad, int rows_per_chunk) {
   constexpr int ROWS = 7, APAIR = 11;
   extern __shared__ char smem[];
-  const int selems = (2 * Wo + 5) * 3;
-  const int sstride = (selems + 4) & ~3;        // f32 elems, 8B-aligned +pad
+  const StripGeom sg = stem7_strip(Wo, 4);      // f32 elems
+  const int sstride = sg.sstride;
   float* xs = reinterpret_cast<float*>(smem);
-  T16* dys = reinterpret_cast<T16*>(smem + ROWS * sstride * 4);
+  T16* dys = reinterpret_cast<T16*>(smem + sg.bytes);
 
   const int k = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -625,49 +607,9 @@ __global__ __launch_bounds__(256) void conv_wgrad_stem7_lds(
   for (long row = row0; row < row1; ++row) {
     const int p = (int)(row % Ho);
     const int n = (int)(row / Ho);
-    const int ih0 = 2 * p - pad;
     __syncthreads();  // previous row's reads done before overwrite
-    {
-      // vectorized fill: strip interior is a contiguous x row (see the
-      // fwd stem kernel comment), short8-loaded and converted
-      const int row3 = 3 * W, off3 = 3 * pad;
-      const int nv8 = (row3 + 7) / 8;
-      for (int t = threadIdx.x; t < ROWS * nv8; t += 256) {
-        const int rr = t / nv8;
-        const int j8 = (t - rr * nv8) * 8;
-        const int ih = ih0 + rr;
-        float* dst = xs + (long)rr * sstride + off3 + j8;
-        if ((row3 & 7) == 0 && (unsigned)ih < (unsigned)H && j8 + 8 <= row3) {
-          const short8 v = *reinterpret_cast<const short8*>(
-              x + ((long)n * H + ih) * row3 + j8);
-#pragma unroll
-          for (int u = 0; u < 8; ++u) dst[u] = s16_to_f32<T16>(v[u]);
-        } else {
-#pragma unroll
-          for (int u = 0; u < 8; ++u) {
-            const int e = j8 + u;
-            dst[u] = (e < row3 && (unsigned)ih < (unsigned)H)
-                         ? F16<T16>::to_f32(
-                               x[((long)n * H + ih) * row3 + e])
-                         : 0.f;
-          }
-        }
-      }
-      for (int t = threadIdx.x; t < ROWS * (sstride - row3); t += 256) {
-        const int nz = sstride - row3;
-        const int rr = t / nz;
-        const int e = t - rr * nz;
-        xs[(long)rr * sstride + (e < off3 ? e : row3 + e)] = 0.f;
-      }
-    }
-    const T16* dyrow = dy + row * Wo * K;
-    if (((Wo * K) & 7) == 0) {
-      for (int i = threadIdx.x * 8; i < Wo * K; i += 256 * 8)
-        *reinterpret_cast<short8*>(dys + i) =
-            *reinterpret_cast<const short8*>(dyrow + i);
-    } else {
-      for (int i = threadIdx.x; i < Wo * K; i += 256) dys[i] = dyrow[i];
-    }
+    strip_fill<ROWS>(xs, x, n, H, W, 2 * p - pad, 3 * pad, sstride);
+    stage_dy_row(dys, dy + row * Wo * K, Wo * K);
     __syncthreads();
 
     for (int q = q0; q < q1; ++q) {
@@ -811,35 +753,63 @@ static inline int out_dim(int in, int k, int stride, int pad) {
   return (in + 2 * pad - k) / stride + 1;
 }
 
-// conv_mfma.hip — MFMA implicit-GEMM path for C%64==0 && K%64==0
-bool conv_mfma_supported(long CI, long KO);
-at::Tensor conv_zero_page(const at::Tensor& like);
-void wgrad_reduce_launch(at::Tensor part, at::Tensor dw, long E, long nz);
-void conv_fwd_mfma_launch(at::Tensor x, at::Tensor w, at::Tensor bias,
-                          at::Tensor y, long stride, long pad, long act,
-                          at::Tensor stats, at::Tensor asc, at::Tensor ash);
-void conv_fwd_mfma_genc_launch(at::Tensor x, at::Tensor wpad, at::Tensor bias,
-                               at::Tensor y, long R, long S, long stride,
-                               long pad, long act);
-void conv_dgrad_mfma_launch(at::Tensor dy, at::Tensor wflip, at::Tensor dx,
-                            long R, long S, long stride, long pad,
-                            at::Tensor addin);
-void conv_wgrad_mfma_launch(at::Tensor x, at::Tensor dy, at::Tensor dw,
-                            long R, long S, long stride, long pad,
-                            at::Tensor asc, at::Tensor ash);
-// stem_mfma.hip — MFMA GEMM stem (7x7/s2/C=3), replaces the dot2 kernels
-bool conv_fwd_stem_gemm_launch(at::Tensor x, at::Tensor w, at::Tensor bias,
-                               at::Tensor y, long pad, long act,
-                               at::Tensor stats, long R, long stride);
-void conv_wgrad_stem_gemm_launch(at::Tensor x, at::Tensor dy, at::Tensor dw,
-                                 long pad, long R, long stride);
-
+// MFMA GEMM stems (stem_mfma.hip) replace the dot2 kernels; =0 disables
 static bool stem_gemm_on() {
-  static const bool v = [] {
-    const char* e = getenv("MI355X_STEM_GEMM");
-    return !e || e[0] != '0';
-  }();
+  static const bool v = EnvKnob("MI355X_STEM_GEMM").on();
   return v;
+}
+
+// conv_fwd_smallc<C_, S_>: the N*P*Q outputs in m-chunks, one per block
+template <int C_, int S_>
+static void fwd_smallc_launch(const at::Tensor& x, const at::Tensor& w,
+                              const at::Tensor& bias, at::Tensor& y,
+                              long stride, long pad, long act) {
+  const int N = x.size(0), H = x.size(1), W = x.size(2);
+  const int P = y.size(1), Q = y.size(2), K = y.size(3);
+  const long M = (long)N * P * Q;
+  const long wrow = w.dim() == 2 ? w.size(1) : (long)S_ * S_ * C_;
+  const SplitPlan sp = split_plan(M, std::min<long>(2048, cdiv_l(M, 256)));
+  const int has_bias = bias.numel() > 0;
+  at::Tensor zp = conv_zero_page(x);
+  DISPATCH_16(x, T16, {
+    launch256(conv_fwd_smallc<T16, C_, S_>, dim3(sp.n), 0,
+              (const T16*)x.data_ptr(), (const T16*)w.data_ptr(),
+              has_bias ? bias.data_ptr<float>() : nullptr,
+              (const T16*)zp.data_ptr(), (T16*)y.data_ptr(), N, H, W, K, P, Q,
+              stride, pad, wrow, act, has_bias, sp.per, M);
+  });
+}
+
+// conv_wgrad_smallc<C_, S_>: grid (m-chunks, filter rows), one partial slab
+// per wave, folded by wgrad_reduce_launch
+template <int C_, int S_>
+static void wgrad_smallc_launch(const at::Tensor& x, const at::Tensor& dy,
+                                at::Tensor& dw, int R, long stride,
+                                long pad) {
+  const int N = x.size(0), H = x.size(1), W = x.size(2);
+  const int P = dy.size(1), Q = dy.size(2), K = dy.size(3);
+  const long M = (long)N * P * Q;
+  const long E = (long)K * R * S_ * C_;
+  const SplitPlan sp = split_plan(
+      M, std::min<long>(std::max<long>(2048 / R, 1), cdiv_l(M, 256)));
+  // empty, not zeros: every slab element is written (acc starts at 0 and
+  // the store runs even for waves with an empty m-range)
+  auto part = at::empty({sp.n * 4, E}, x.options().dtype(at::kFloat));
+  at::Tensor zp = conv_zero_page(x);
+  DISPATCH_16(x, T16, {
+    launch256(conv_wgrad_smallc<T16, C_, S_>, dim3((unsigned)sp.n, R), 0,
+              (const T16*)x.data_ptr(), (const T16*)dy.data_ptr(),
+              (const T16*)zp.data_ptr(), part.data_ptr<float>(), N, H, W, K,
+              P, Q, R, stride, pad, sp.per, M);
+  });
+  wgrad_reduce_launch(part, dw, E, sp.n * 4);
+}
+
+// row-chunk plan of the LDS stem wgrads: 512 blocks x 4 waves at occupancy
+// 2 fills the chip exactly once; fewer chunks = 4x less partial-slab
+// traffic for the reduce
+static SplitPlan stem_rows_plan(long nrows) {
+  return split_plan(nrows, std::min<long>(512, nrows));
 }
 
 at::Tensor conv2d_fwd(at::Tensor x, at::Tensor w, at::Tensor bias,
@@ -862,23 +832,15 @@ at::Tensor conv2d_fwd(at::Tensor x, at::Tensor w, at::Tensor bias,
     return y;
   }
   if (stem7) {
-    const long M = (long)N * P * Q;
     const long wrow = w.dim() == 2 ? w.size(1) : (long)R * S * C;
-    long nchunks = std::min<long>(2048, cdiv_l(M, 256));
-    const long m_per_chunk = cdiv_l(M, std::max<long>(nchunks, 1));
-    nchunks = cdiv_l(M, m_per_chunk);
     const int has_bias = bias.numel() > 0;
-    at::Tensor zp = conv_zero_page(x);
-    const int selems = (2 * Q + 5) * 3;
-    const int sstride = (selems + 4) & ~3;
-    const size_t smem = (size_t)7 * sstride * x.element_size();
+    const size_t smem = stem7_strip(Q, x.element_size()).bytes;
     DISPATCH_16(x, T16, {
-      hipLaunchKernelGGL((conv_fwd_stem7_lds<T16>), dim3((unsigned)(N * P)),
-                         dim3(256), smem, cur_stream(),
-                         (const T16*)x.data_ptr(), (const T16*)w.data_ptr(),
-                         has_bias ? bias.data_ptr<float>() : nullptr,
-                         (T16*)y.data_ptr(), N, H, W, K, P, Q, (int)pad,
-                         wrow, (int)act, has_bias);
+      launch256(conv_fwd_stem7_lds<T16>, dim3((unsigned)(N * P)), smem,
+                (const T16*)x.data_ptr(), (const T16*)w.data_ptr(),
+                has_bias ? bias.data_ptr<float>() : nullptr,
+                (T16*)y.data_ptr(), N, H, W, K, P, Q, pad, wrow, act,
+                has_bias);
     });
     return y;
   }
@@ -893,50 +855,23 @@ at::Tensor conv2d_fwd(at::Tensor x, at::Tensor w, at::Tensor bias,
   if (K <= 64 && C == 3 && R == 3 && S == 3 && stride == 1 && pad == 1 &&
       P == H && Q == W) {
     const long wrow = w.dim() == 2 ? w.size(1) : 27L;
-    const int selems = (Q + 2) * 3;
-    const int sstride = (selems + 4) & ~3;
-    const size_t smem = (size_t)3 * sstride * 4;
+    const size_t smem = stem3_strip(Q).bytes;
     const int has_bias = bias.numel() > 0;
     DISPATCH_16(x, T16, {
-      hipLaunchKernelGGL((conv_fwd_stem3_lds<T16>), dim3((unsigned)(N * P)),
-                         dim3(256), smem, cur_stream(),
-                         (const T16*)x.data_ptr(), (const T16*)w.data_ptr(),
-                         has_bias ? bias.data_ptr<float>() : nullptr,
-                         (T16*)y.data_ptr(), N, H, W, K, P, Q, wrow,
-                         (int)act, has_bias);
+      launch256(conv_fwd_stem3_lds<T16>, dim3((unsigned)(N * P)), smem,
+                (const T16*)x.data_ptr(), (const T16*)w.data_ptr(),
+                has_bias ? bias.data_ptr<float>() : nullptr,
+                (T16*)y.data_ptr(), N, H, W, K, P, Q, wrow, act, has_bias);
     });
     return y;
   }
   const bool smallc_fwd = K <= 64 && R == 3 && S == 3 && (C == 3 || C == 6) &&
                           (stride == 1 || stride == 2);
   if (smallc_fwd) {
-    const long M = (long)N * P * Q;
-    const long wrow = w.dim() == 2 ? w.size(1) : (long)R * S * C;
-    long nchunks = std::min<long>(2048, cdiv_l(M, 256));
-    const long m_per_chunk = cdiv_l(M, std::max<long>(nchunks, 1));
-    nchunks = cdiv_l(M, m_per_chunk);
-    const int has_bias = bias.numel() > 0;
-    at::Tensor zp = conv_zero_page(x);
-    DISPATCH_16(x, T16, {
-      if (C == 3)
-        hipLaunchKernelGGL((conv_fwd_smallc<T16, 3, 3>), dim3(nchunks),
-                           dim3(256), 0, cur_stream(),
-                           (const T16*)x.data_ptr(), (const T16*)w.data_ptr(),
-                           has_bias ? bias.data_ptr<float>() : nullptr,
-                           (const T16*)zp.data_ptr(),
-                           (T16*)y.data_ptr(), N, H, W, K, P, Q, (int)stride,
-                           (int)pad, wrow, (int)act, has_bias, m_per_chunk,
-                           M);
-      else
-        hipLaunchKernelGGL((conv_fwd_smallc<T16, 6, 3>), dim3(nchunks),
-                           dim3(256), 0, cur_stream(),
-                           (const T16*)x.data_ptr(), (const T16*)w.data_ptr(),
-                           has_bias ? bias.data_ptr<float>() : nullptr,
-                           (const T16*)zp.data_ptr(),
-                           (T16*)y.data_ptr(), N, H, W, K, P, Q, (int)stride,
-                           (int)pad, wrow, (int)act, has_bias, m_per_chunk,
-                           M);
-    });
+    if (C == 3)
+      fwd_smallc_launch<3, 3>(x, w, bias, y, stride, pad, act);
+    else
+      fwd_smallc_launch<6, 3>(x, w, bias, y, stride, pad, act);
     return y;
   }
   if (w.dim() == 2) {  // padded [KO,KGP] weight: generic small-C MFMA path
@@ -952,12 +887,10 @@ at::Tensor conv2d_fwd(at::Tensor x, at::Tensor w, at::Tensor bias,
   const long total = (long)N * P * Q * K;
   const int has_bias = bias.numel() > 0;
   DISPATCH_16(x, T16, {
-    hipLaunchKernelGGL(conv_fwd_direct<T16>, conv_grid(total), dim3(256), 0,
-                       cur_stream(), (const T16*)x.data_ptr(),
-                       (const T16*)w.data_ptr(),
-                       has_bias ? bias.data_ptr<float>() : nullptr,
-                       (T16*)y.data_ptr(), N, H, W, C, K, R, S, P, Q,
-                       (int)stride, (int)pad, (int)act, has_bias);
+    launch256(conv_fwd_direct<T16>, conv_grid(total), 0,
+              (const T16*)x.data_ptr(), (const T16*)w.data_ptr(),
+              has_bias ? bias.data_ptr<float>() : nullptr, (T16*)y.data_ptr(),
+              N, H, W, C, K, R, S, P, Q, stride, pad, act, has_bias);
   });
   return y;
 }
@@ -1070,11 +1003,9 @@ at::Tensor conv2d_dgrad(at::Tensor dy, at::Tensor wflip, long stride,
               "addin requires the MFMA dgrad path (C,K % 64 == 0)");
   const long total = (long)N * H * W * C;
   DISPATCH_16(dy, T16, {
-    hipLaunchKernelGGL(conv_dgrad_direct<T16>, conv_grid(total), dim3(256), 0,
-                       cur_stream(), (const T16*)dy.data_ptr(),
-                       (const T16*)wflip.data_ptr(), (T16*)dx.data_ptr(), N,
-                       (int)H, (int)W, C, K, R, S, P, Q, (int)stride,
-                       (int)pad);
+    launch256(conv_dgrad_direct<T16>, conv_grid(total), 0,
+              (const T16*)dy.data_ptr(), (const T16*)wflip.data_ptr(),
+              (T16*)dx.data_ptr(), N, H, W, C, K, R, S, P, Q, stride, pad);
   });
   return dx;
 }
@@ -1104,97 +1035,48 @@ at::Tensor conv2d_wgrad(at::Tensor x, at::Tensor dy, long R, long S,
   }
   if (K <= 64 && C == 3 && R == 3 && S == 3 && stride == 1 && pad == 1 &&
       P == H && Q == W) {
-    const long nrows = (long)N * P;
-    long nc = std::min<long>(512, nrows);
-    const int rows_per_chunk = (int)cdiv_l(nrows, nc);
-    nc = cdiv_l(nrows, rows_per_chunk);
+    const SplitPlan rp = stem_rows_plan((long)N * P);
     const long E = (long)K * 27;
     auto dw = at::empty({K, 3L, 3L, 3L}, x.options().dtype(at::kFloat));
-    auto partl = at::empty({nc * 4, E}, x.options().dtype(at::kFloat));
-    const int selems = (Q + 2) * 3;
-    const int sstride = (selems + 4) & ~3;
-    const size_t smem = (size_t)3 * sstride * 4 + (size_t)Q * K * 2;
+    auto partl = at::empty({rp.n * 4, E}, x.options().dtype(at::kFloat));
+    const size_t smem = stem3_strip(Q).bytes + (size_t)Q * K * 2;
     DISPATCH_16(x, T16, {
-      hipLaunchKernelGGL((conv_wgrad_stem3_lds<T16>), dim3((unsigned)nc),
-                         dim3(256), smem, cur_stream(),
-                         (const T16*)x.data_ptr(), (const T16*)dy.data_ptr(),
-                         partl.data_ptr<float>(), N, H, W, K, P, Q,
-                         rows_per_chunk);
+      launch256(conv_wgrad_stem3_lds<T16>, dim3((unsigned)rp.n), smem,
+                (const T16*)x.data_ptr(), (const T16*)dy.data_ptr(),
+                partl.data_ptr<float>(), N, H, W, K, P, Q, rp.per);
     });
-    wgrad_reduce_launch(partl, dw, E, nc * 4);
+    wgrad_reduce_launch(partl, dw, E, rp.n * 4);
     return dw;
   }
   const bool smallc = K <= 64 &&
       ((C == 3 && (S == 3 || S == 5 || S == 7)) || (C == 6 && S == 5));
   if (smallc) {
     const long E = (long)K * R * S * C;
-    long nchunks = std::min<long>(std::max<long>(2048 / R, 1),
-                                  cdiv_l(M, 256));
-    const long m_per_chunk = cdiv_l(M, nchunks);
-    nchunks = cdiv_l(M, m_per_chunk);
     auto dw = at::empty({K, (long)C, R, S}, x.options().dtype(at::kFloat));
     if (C == 3 && S == 7 && stride == 2 && pad <= 4) {
       if (K % 64 == 0 && R == 7 && pad <= 3 && stem_gemm_on()) {
         conv_wgrad_stem_gemm_launch(x, dy, dw, pad, 7, 2);
         return dw;
       }
-      const long nrows = (long)N * P;
-      // 512 blocks x 4 waves at occupancy 2 fills the chip exactly once;
-      // fewer chunks = 4x less partial-slab traffic for the reduce
-      long nc = std::min<long>(512, nrows);
-      const int rows_per_chunk = (int)cdiv_l(nrows, nc);
-      nc = cdiv_l(nrows, rows_per_chunk);
-      auto partl = at::empty({nc * 4, E}, x.options().dtype(at::kFloat));
-      const int selems = (2 * Q + 5) * 3;
-      const int sstride = (selems + 4) & ~3;
-      const size_t smem = (size_t)7 * sstride * 4 + (size_t)Q * K * 2;
+      const SplitPlan rp = stem_rows_plan((long)N * P);
+      auto partl = at::empty({rp.n * 4, E}, x.options().dtype(at::kFloat));
+      const size_t smem = stem7_strip(Q, 4).bytes + (size_t)Q * K * 2;
       DISPATCH_16(x, T16, {
-        hipLaunchKernelGGL((conv_wgrad_stem7_lds<T16>), dim3((unsigned)nc),
-                           dim3(256), smem, cur_stream(),
-                           (const T16*)x.data_ptr(),
-                           (const T16*)dy.data_ptr(),
-                           partl.data_ptr<float>(), N, H, W, K, P, Q,
-                           (int)pad, rows_per_chunk);
+        launch256(conv_wgrad_stem7_lds<T16>, dim3((unsigned)rp.n), smem,
+                  (const T16*)x.data_ptr(), (const T16*)dy.data_ptr(),
+                  partl.data_ptr<float>(), N, H, W, K, P, Q, pad, rp.per);
       });
-      wgrad_reduce_launch(partl, dw, E, nc * 4);
+      wgrad_reduce_launch(partl, dw, E, rp.n * 4);
       return dw;
     }
-    // empty, not zeros: every slab element is written (acc starts at 0 and
-    // the store runs even for waves with an empty m-range)
-    auto part = at::empty({nchunks * 4, E}, x.options().dtype(at::kFloat));
-    at::Tensor zpw = conv_zero_page(x);
-    dim3 grid((unsigned)nchunks, R);
-    DISPATCH_16(x, T16, {
-      if (C == 3 && S == 3)
-        hipLaunchKernelGGL((conv_wgrad_smallc<T16, 3, 3>), grid, dim3(256), 0,
-                           cur_stream(), (const T16*)x.data_ptr(),
-                           (const T16*)dy.data_ptr(),
-                           (const T16*)zpw.data_ptr(), part.data_ptr<float>(),
-                           N, H, W, K, P, Q, R, (int)stride, (int)pad,
-                           m_per_chunk, M);
-      else if (C == 3 && S == 5)
-        hipLaunchKernelGGL((conv_wgrad_smallc<T16, 3, 5>), grid, dim3(256), 0,
-                           cur_stream(), (const T16*)x.data_ptr(),
-                           (const T16*)dy.data_ptr(),
-                           (const T16*)zpw.data_ptr(), part.data_ptr<float>(),
-                           N, H, W, K, P, Q, R, (int)stride, (int)pad,
-                           m_per_chunk, M);
-      else if (C == 3 && S == 7)
-        hipLaunchKernelGGL((conv_wgrad_smallc<T16, 3, 7>), grid, dim3(256), 0,
-                           cur_stream(), (const T16*)x.data_ptr(),
-                           (const T16*)dy.data_ptr(),
-                           (const T16*)zpw.data_ptr(), part.data_ptr<float>(),
-                           N, H, W, K, P, Q, R, (int)stride, (int)pad,
-                           m_per_chunk, M);
-      else
-        hipLaunchKernelGGL((conv_wgrad_smallc<T16, 6, 5>), grid, dim3(256), 0,
-                           cur_stream(), (const T16*)x.data_ptr(),
-                           (const T16*)dy.data_ptr(),
-                           (const T16*)zpw.data_ptr(), part.data_ptr<float>(),
-                           N, H, W, K, P, Q, R, (int)stride, (int)pad,
-                           m_per_chunk, M);
-    });
-    wgrad_reduce_launch(part, dw, E, nchunks * 4);
+    if (C == 3 && S == 3)
+      wgrad_smallc_launch<3, 3>(x, dy, dw, R, stride, pad);
+    else if (C == 3 && S == 5)
+      wgrad_smallc_launch<3, 5>(x, dy, dw, R, stride, pad);
+    else if (C == 3 && S == 7)
+      wgrad_smallc_launch<3, 7>(x, dy, dw, R, stride, pad);
+    else
+      wgrad_smallc_launch<6, 5>(x, dy, dw, R, stride, pad);
     return dw;
   }
   // split the NPQ reduction so small filters still fill the chip
@@ -1208,11 +1090,9 @@ at::Tensor conv2d_wgrad(at::Tensor x, at::Tensor dy, long R, long S,
                   : at::empty({nchunks, total_w}, x.options().dtype(at::kFloat));
   dim3 grid((unsigned)std::min<long>(cdiv_l(total_w, 256), 4096), nchunks);
   DISPATCH_16(x, T16, {
-    hipLaunchKernelGGL(conv_wgrad_direct<T16>, grid, dim3(256), 0,
-                       cur_stream(), (const T16*)x.data_ptr(),
-                       (const T16*)dy.data_ptr(), part.data_ptr<float>(), N,
-                       H, W, C, K, (int)R, (int)S, P, Q, (int)stride, (int)pad,
-                       m_per_chunk);
+    launch256(conv_wgrad_direct<T16>, grid, 0, (const T16*)x.data_ptr(),
+              (const T16*)dy.data_ptr(), part.data_ptr<float>(), N, H, W, C,
+              K, R, S, P, Q, stride, pad, m_per_chunk);
   });
   if (nchunks > 1) fold_rows(part, dw, total_w, nchunks);
   return dw;

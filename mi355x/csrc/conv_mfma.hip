@@ -12,7 +12,7 @@
 // tile, 4 waves x (32M x 64N) each as 2 x mfma_f32_32x32x16, LDS tiles
 // [row][BK+8] padded against bank conflicts (G4), T14-style staging
 // (write after barrier, next global load issued under the MFMA phase).
-#include "common.h"
+#include "conv_internal.h"
 
 typedef __attribute__((ext_vector_type(8))) _Float16 half8;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
@@ -555,9 +555,8 @@ void stats_slab_reduce(at::Tensor slab, at::Tensor stats, int gx, int bnt2,
     const int bpb1 = (int)cdiv_l(gx, 1024);
     const int gx2 = (int)cdiv_l(gx, bpb1);
     auto l2 = at::empty({(long)by * gx2 * bnt2}, slab.options());
-    hipLaunchKernelGGL(conv_stats_partial, dim3(gx2, by), dim3(256), 0,
-                       cur_stream(), slab.data_ptr<float>(),
-                       l2.data_ptr<float>(), gx, bnt2, bpb1);
+    launch256(conv_stats_partial, dim3(gx2, by), 0, slab.data_ptr<float>(),
+              l2.data_ptr<float>(), gx, bnt2, bpb1);
     slab = l2;
     gx = gx2;
   }
@@ -565,15 +564,13 @@ void stats_slab_reduce(at::Tensor slab, at::Tensor stats, int gx, int bnt2,
     const int bpb2 = (int)cdiv_l(gx, 64);
     const int gx3 = (int)cdiv_l(gx, bpb2);
     auto l3 = at::empty({(long)by * gx3 * bnt2}, slab.options());
-    hipLaunchKernelGGL(conv_stats_partial, dim3(gx3, by), dim3(256), 0,
-                       cur_stream(), slab.data_ptr<float>(),
-                       l3.data_ptr<float>(), gx, bnt2, bpb2);
+    launch256(conv_stats_partial, dim3(gx3, by), 0, slab.data_ptr<float>(),
+              l3.data_ptr<float>(), gx, bnt2, bpb2);
     slab = l3;
     gx = gx3;
   }
-  hipLaunchKernelGGL(conv_stats_reduce, dim3(1, by), dim3(256), 0,
-                     cur_stream(), slab.data_ptr<float>(),
-                     stats.data_ptr<float>(), gx, bnt2, C, gx);
+  launch256(conv_stats_reduce, dim3(1, by), 0, slab.data_ptr<float>(),
+            stats.data_ptr<float>(), gx, bnt2, C, gx);
 }
 
 // ---------------------------------------------------------------------------
@@ -1418,298 +1415,10 @@ __global__ void wgrad_reduce_chunks(const float* __restrict__ part,
 
 }  // namespace
 
-// ---------------------------------------------------------------------------
-// glds-pipelined fwd variant: the A (gathered input) tile is staged by
-// `global_load_lds` (direct HBM->LDS DMA, no VGPR round-trip, no ds_write
-// pass — guide §5 ladder step 3) into a double-buffered LINEAR [BM][BK]
-// image with an XOR-swizzled SOURCE address (rule 21: linear dest +
-// inverse-swizzled source + swizzled read), zero-page redirect for
-// padding rows. ONE __syncthreads per k-step: its implicit vmcnt(0)
-// drains the in-flight DMA for the NEXT step's buffer while this step's
-// MFMA runs above it.
-// ---------------------------------------------------------------------------
-namespace {
-
-template <typename T16, int NT>
-__global__ __launch_bounds__(256) void conv_fwd_glds(
-    const T16* __restrict__ in, const T16* __restrict__ wgt,
-    const float* __restrict__ bias, const T16* __restrict__ zpage,
-    T16* __restrict__ out, const int N, const int Hi, const int Wi,
-    const int CI, const int KO, const int Ho, const int Wo, const int R,
-    const int S, const int stride, const int pad, const int act,
-    const int has_bias) {
-  constexpr int BNT = NT * 32;
-  __shared__ T16 lds[2 * BM * BK + 2 * BNT * LDK];
-
-  const int tid = threadIdx.x;
-  const long Mtot = (long)N * Ho * Wo;
-  const long bm0 = (long)blockIdx.x * BM;
-  const int k0 = blockIdx.y * BNT;
-  const int wave = tid >> 6;
-  const int lane = tid & 63;
-  const int li = lane & 31;
-  const int kh = lane >> 5;
-  const int wm = wave * 32;
-
-  // ---- A rows this lane feeds (4 glds per wave, 8 rows each) ----
-  const int lr = lane >> 3;          // row-within-8 of each glds
-  const int ce = (lane & 7) * 8;     // element col of the 16B piece
-  const int swz = lr * 8;            // XOR swizzle, elements ((r&7)<<4 B)
-  long nbase[4];
-  int ih0v[4], iw0v[4];
-  bool mokv[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int r = 32 * wave + 8 * i + lr;
-    const long m = bm0 + r;
-    mokv[i] = m < Mtot;
-    int n_ = 0, p_ = 0, q_ = 0;
-    if (mokv[i]) {
-      n_ = (int)(m / ((long)Ho * Wo));
-      const int pq = (int)(m % ((long)Ho * Wo));
-      p_ = pq / Wo;
-      q_ = pq % Wo;
-    }
-    nbase[i] = (long)n_ * Hi * Wi * CI;
-    ih0v[i] = p_ * stride - pad;
-    iw0v[i] = q_ * stride - pad;
-  }
-
-  // ---- B staging (register -> LDS, padded LDK rows) ----
-  constexpr int TPR = 256 / BNT;
-  constexpr int EPT = BK / TPR;
-  const int sb_n = tid / TPR;
-  const int sb_c = (tid % TPR) * EPT;
-  const T16* wrow = wgt + (long)(k0 + sb_n) * R * S * CI + sb_c;
-  short8 sb[EPT / 8];
-
-  const int cchunks = CI / BK;
-  const int ksteps = R * S * cchunks;
-
-  auto issue_gldsA = [&](int j, int buf) {
-    const int c0 = (j % cchunks) * BK;
-    const int s_ = (j / cchunks) % S;
-    const int r_ = j / (cchunks * S);
-    T16* dstA = lds + buf * (BM * BK);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int ih = ih0v[i] + r_;
-      const int iw = iw0v[i] + s_;
-      const bool ok = mokv[i] && (unsigned)ih < (unsigned)Hi &&
-                      (unsigned)iw < (unsigned)Wi;
-      const T16* src =
-          ok ? in + nbase[i] + ((long)ih * Wi + iw) * CI + c0 + (ce ^ swz)
-             : zpage + (ce ^ swz);
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)src,
-          (__attribute__((address_space(3))) void*)(dstA +
-                                                    (32 * wave + 8 * i) * BK),
-          16, 0, 0);
-    }
-  };
-  auto load_B = [&](int j) {
-    const int c0 = (j % cchunks) * BK;
-    const int s_ = (j / cchunks) % S;
-    const int r_ = j / (cchunks * S);
-    const T16* wp = wrow + (long)(r_ * S + s_) * CI + c0;
-#pragma unroll
-    for (int i = 0; i < EPT / 8; ++i)
-      sb[i] = *reinterpret_cast<const short8*>(wp + 8 * i);
-  };
-  auto stage_B = [&](int buf) {
-    short* pb = reinterpret_cast<short*>(lds + 2 * BM * BK + buf * BNT * LDK +
-                                         sb_n * LDK + sb_c);
-#pragma unroll
-    for (int i = 0; i < EPT / 8; ++i)
-      *reinterpret_cast<short8*>(pb + 8 * i) = sb[i];
-  };
-
-  f32x16 acc[NT] = {};
-
-  issue_gldsA(0, 0);
-  load_B(0);
-  stage_B(0);
-  __syncthreads();  // drains glds(0) (implicit vmcnt 0) + B writes
-  for (int j = 0; j < ksteps; ++j) {
-    const int nxt = (j + 1) & 1;
-    if (j + 1 < ksteps) {
-      issue_gldsA(j + 1, nxt);  // DMA runs under this step's MFMA
-      load_B(j + 1);
-    }
-    const T16* ldsA = lds + (j & 1) * (BM * BK);
-    const T16* ldsB = lds + 2 * BM * BK + (j & 1) * BNT * LDK;
-#pragma unroll
-    for (int kk = 0; kk < BK; kk += 16) {
-      const int m = wm + li;
-      const short8 af = *reinterpret_cast<const short8*>(
-          ldsA + m * BK + ((kk + kh * 8) ^ ((m & 7) * 8)));
-#pragma unroll
-      for (int tnt = 0; tnt < NT; ++tnt) {
-        const short8 bf = *reinterpret_cast<const short8*>(
-            ldsB + (tnt * 32 + li) * LDK + kk + kh * 8);
-        acc[tnt] = Mfma32<T16>::run(af, bf, acc[tnt]);
-      }
-    }
-    if (j + 1 < ksteps) stage_B(nxt);  // B reg latency hid under the MFMAs
-    __syncthreads();
-  }
-
-  float bv[NT];
-#pragma unroll
-  for (int tnt = 0; tnt < NT; ++tnt)
-    bv[tnt] = has_bias ? bias[k0 + tnt * 32 + li] : 0.f;
-#pragma unroll
-  for (int reg = 0; reg < 16; ++reg) {
-    const int row = (reg & 3) + 8 * (reg >> 2) + 4 * kh;
-    const long m_out = bm0 + wm + row;
-    if (m_out < Mtot) {
-#pragma unroll
-      for (int tnt = 0; tnt < NT; ++tnt) {
-        float v = acc[tnt][reg] + bv[tnt];
-        if (act == 1) v = fmaxf(v, 0.f);
-        out[m_out * KO + k0 + tnt * 32 + li] = F16<T16>::from_f32(v);
-      }
-    }
-  }
-}
-
-}  // namespace
-
-// ---------------------------------------------------------------------------
-// halo wgrad for the dominant 3x3/stride-1/pad-1 convs: ONE block computes
-// all NINE taps of a 64(KO) x 64(CI) dw tile over its m-chunk, so dy and x
-// are staged ONCE per 64-pixel m-step instead of once per tap (the tap-
-// per-block kernel re-reads each ~9x and measured HBM/L3-traffic-bound).
-// x is staged as a zero-bordered 2-D spatial halo image [(64/W)+2 rows]
-// [W+2 cols][64 ch]; tap (r,s) of pixel (p,q) reads image[p-prow0+r][q+s]
-// so padding needs no per-element masking. The b-fragment m-gather is 8
-// scalar u16 LDS reads with power-of-two (W) row decode.
-// ---------------------------------------------------------------------------
-
-namespace {
-
-constexpr int HALO_IMG_MAX = 224;  // pixels: covers W=8..64 (+2 halo rows)
-
-template <typename T16>
-__global__ __launch_bounds__(256) void conv_wgrad_halo3(
-    const T16* __restrict__ x,   // [N,H,W,CI]
-    const T16* __restrict__ dy,  // [M,KO]
-    float* __restrict__ part,    // [nchunks][KO*CI*9] (KCRS slabs)
-    const int N, const int H, const int W, const int CI, const int KO,
-    const int wshift, const long m_per_chunk) {
-  __shared__ T16 lds[64 * LDM + HALO_IMG_MAX * 64];
-  T16* dyT = lds;                 // [64 k][LDM m]
-  T16* ximg = lds + 64 * LDM;     // [pix][64 c]
-
-  const int tid = threadIdx.x;
-  const long Mtot = (long)N * H * W;
-  const int k0 = blockIdx.x * 64;
-  const int c0 = blockIdx.y * 64;
-  const long m_begin = (long)blockIdx.z * m_per_chunk;
-  const long m_end = min(Mtot, m_begin + m_per_chunk);
-
-  const int RW = 64 >> wshift;    // pixel rows per m-step
-  const int IMG_C = W + 2;
-  const int npix = (RW + 2) * IMG_C;
-
-  // dyT staging (threads 0..127): 4 m-rows x 8 k each, transposed write
-  const int t7 = tid & 127;
-  const int sm = (t7 & 15) * 4;
-  const int sk = (t7 >> 4) * 8;
-  // ximg staging (all 256): 4 threads per pixel, 16 channels each
-  const int px_slot = tid >> 2;
-  const int px_c = (tid & 3) * 16;
-
-  const int wave = tid >> 6;
-  const int lane = tid & 63;
-  const int li = lane & 31;
-  const int kh = lane >> 5;
-  const int i0 = (wave & 1) * 32;   // KO half
-  const int j0 = (wave >> 1) * 32;  // CI half
-
-  f32x16 acc[9] = {};
-
-  // uniform per-step position (advanced incrementally below)
-  int n_ = (int)(m_begin / ((long)H * W));
-  int prow0 = (int)((m_begin % ((long)H * W)) >> wshift);
-
-  for (long m0 = m_begin; m0 < m_end; m0 += 64) {
-    __syncthreads();  // previous MFMA phase done with LDS
-    // ---- stage dyT ----
-    if (tid < 128) {
-      short8 v[4];
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi)
-        v[mi] = *reinterpret_cast<const short8*>(dy + (m0 + sm + mi) * KO +
-                                                 k0 + sk);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        short4v pk = {v[0][e], v[1][e], v[2][e], v[3][e]};
-        *reinterpret_cast<short4v*>(
-            reinterpret_cast<short*>(dyT + (sk + e) * LDM + sm)) = pk;
-      }
-    }
-    // ---- stage the zero-bordered x halo image ----
-    for (int pix = px_slot; pix < npix; pix += 64) {
-      const int ir = pix / IMG_C;
-      const int ic = pix - ir * IMG_C;
-      const int p_src = prow0 - 1 + ir;
-      const int q_src = ic - 1;
-      const bool ok = (unsigned)p_src < (unsigned)H &&
-                      (unsigned)q_src < (unsigned)W;
-      short8 a = {}, b = {};
-      if (ok) {
-        const T16* src =
-            x + (((long)n_ * H + p_src) * W + q_src) * CI + c0 + px_c;
-        a = *reinterpret_cast<const short8*>(src);
-        b = *reinterpret_cast<const short8*>(src + 8);
-      }
-      short* dst = reinterpret_cast<short*>(ximg + (long)pix * 64 + px_c);
-      *reinterpret_cast<short8*>(dst) = a;
-      *reinterpret_cast<short8*>(dst + 8) = b;
-    }
-    __syncthreads();
-    // ---- 4 k-steps x 9 taps of MFMA ----
-#pragma unroll
-    for (int kk = 0; kk < 64; kk += 16) {
-      const short8 af = *reinterpret_cast<const short8*>(
-          dyT + (i0 + li) * LDM + kk + kh * 8);
-#pragma unroll
-      for (int tap = 0; tap < 9; ++tap) {
-        const int r = tap / 3, ss = tap % 3;
-        short8 bf;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const int mrel = kk + kh * 8 + e;
-          const int prow = mrel >> wshift;
-          const int pcol = mrel & (W - 1);
-          bf[e] = *reinterpret_cast<const short*>(
-              ximg + ((long)(prow + r) * IMG_C + pcol + ss) * 64 + j0 + li);
-        }
-        acc[tap] = Mfma32<T16>::run(af, bf, acc[tap]);
-      }
-    }
-    prow0 += RW;
-    if (prow0 == H) {
-      prow0 = 0;
-      ++n_;
-    }
-  }
-
-  // ---- per-chunk slab store, parameter layout [KO,CI,3,3] ----
-  float* slab = part + (long)blockIdx.z * ((long)KO * CI * 9);
-#pragma unroll
-  for (int tap = 0; tap < 9; ++tap) {
-#pragma unroll
-    for (int reg = 0; reg < 16; ++reg) {
-      const int i = (reg & 3) + 8 * (reg >> 2) + 4 * kh;
-      slab[((long)(k0 + i0 + i) * CI + c0 + j0 + li) * 9 + tap] =
-          acc[tap][reg];
-    }
-  }
-}
-
-}  // namespace
+// host launchers --------------------------------------------------------
+// One launch function per kernel family: it writes the argument list once
+// and picks the compile-time variant. The variants are not full cross
+// products; each pick<> lists exactly the ones that exist.
 
 bool conv_mfma_supported(long CI, long KO) {
   return CI % 64 == 0 && KO % 64 == 0;
@@ -1741,434 +1450,340 @@ void wgrad_reduce_launch(at::Tensor part, at::Tensor dw, long E, long nz) {
     auto tmp = at::empty({zc, E}, part.options());
     const long per = cdiv_l(nz, zc);
     zc = cdiv_l(nz, per);
-    hipLaunchKernelGGL(wgrad_reduce_zchunk, dim3(eblocks, (unsigned)zc),
-                       dim3(256), 0, cur_stream(), part.data_ptr<float>(),
-                       tmp.data_ptr<float>(), E, (int)nz, (int)per);
-    hipLaunchKernelGGL(wgrad_reduce_chunks, dim3(eblocks), dim3(256), 0,
-                       cur_stream(), tmp.data_ptr<float>(),
-                       dw.data_ptr<float>(), E, (int)zc);
+    launch256(wgrad_reduce_zchunk, dim3(eblocks, (unsigned)zc), 0,
+              part.data_ptr<float>(), tmp.data_ptr<float>(), E, nz, per);
+    launch256(wgrad_reduce_chunks, dim3(eblocks), 0, tmp.data_ptr<float>(),
+              dw.data_ptr<float>(), E, zc);
     return;
   }
-  hipLaunchKernelGGL(wgrad_reduce_chunks, dim3(eblocks), dim3(256), 0,
-                     cur_stream(), part.data_ptr<float>(),
-                     dw.data_ptr<float>(), E, (int)nz);
+  launch256(wgrad_reduce_chunks, dim3(eblocks), 0, part.data_ptr<float>(),
+            dw.data_ptr<float>(), E, nz);
 }
+
+namespace {
+
+bool present(const at::Tensor& t) { return t.defined() && t.numel() > 0; }
+float* f32_or_null(const at::Tensor& t) {
+  return present(t) ? t.data_ptr<float>() : nullptr;
+}
+
+// knobs that more than one launcher reads
+long wgrad_chunk_cap() {  // ablation knob: at most this many m-chunks
+  static const long v = EnvKnob("MI355X_WGRAD_CHUNKS").num(0);
+  return v;
+}
+bool conv_patch_on() {  // =0 falls back to the per-tap gather (fwd, dgrad)
+  static const bool v = EnvKnob("MI355X_CONV_PATCH").on();
+  return v;
+}
+
+// ---- wgrad ------------------------------------------------------------
+// what the three wgrad kernel families share
+struct WgradArgs {
+  at::Tensor x, dy;
+  const float *asc, *ash;  // lazy-BN transform of the x operand, or null
+  int N, Hi, Wi, CI, KO, Ho, Wo, R, S, stride, pad;
+};
+
+// the staging variants that exist (there is no SCALED + KMIN kernel)
+enum WgradMode { WG_PLAIN, WG_SCALED, WG_KMIN };
+WgradMode wgrad_mode(const WgradArgs& a, bool kmin_knob) {
+  return a.asc ? WG_SCALED : kmin_knob ? WG_KMIN : WG_PLAIN;
+}
+
+// Split-M plan of an MFMA wgrad: chunks of a multiple of WGM rows. One
+// chunk stores straight into dw; several store one partial filter each,
+// which wgrad_split_finish folds in order.
+// A/B on layer1 b256 (partial slabs): m/chunk 1216 -> 189us, 4096 ->
+// 137us, 16384 -> 327us: the lever is PER-CHUNK depth (~4096 m), which
+// also holds as M grows with batch (576-total-blocks regressed b1024)
+struct WgradSplit {
+  long m_per_chunk;
+  int nchunks;
+  long E;
+  at::Tensor part;
+};
+WgradSplit wgrad_split(long M, long E, const at::Tensor& dw, long cap) {
+  long want = std::min<long>(cdiv_l(M, 4096), 4096);
+  if (cap > 0) want = std::min(want, cap);
+  const SplitPlan p = split_plan(M, want, WGM);
+  return {p.per, (int)p.n, E,
+          p.n > 1 ? at::empty({p.n, E}, dw.options()) : dw};
+}
+void wgrad_split_finish(const WgradSplit& sp, const at::Tensor& dw) {
+  if (sp.nchunks > 1) wgrad_reduce_launch(sp.part, dw, sp.E, sp.nchunks);
+}
+
+// conv_wgrad_mfma_s3: KT=128 exists as the plain kernel only
+void wgrad_s3_launch(const WgradArgs& a, int KT, WgradMode mode,
+                     const WgradSplit& sp) {
+  dim3 grid(a.KO / KT, 3 * (a.CI / 64), sp.nchunks);
+  DISPATCH_16(a.x, T16, {
+    auto go = [&](auto kern) {
+      launch256(kern, grid, 0, (const T16*)a.x.data_ptr(),
+                (const T16*)a.dy.data_ptr(), a.asc, a.ash,
+                sp.part.data_ptr<float>(), a.N, a.Hi, a.Wi, a.CI, a.KO, a.Ho,
+                a.Wo, sp.m_per_chunk, sp.nchunks);
+    };
+    if (KT == 128)
+      go(conv_wgrad_mfma_s3<T16, 128>);
+    else
+      pick<WG_PLAIN, WG_SCALED, WG_KMIN>(mode, [&](auto m) {
+        constexpr WgradMode M_ = decltype(m)::value;
+        go(conv_wgrad_mfma_s3<T16, 64, M_ == WG_SCALED, M_ == WG_KMIN>);
+      });
+  });
+}
+
+void wgrad_t128_launch(const WgradArgs& a, WgradMode mode,
+                       const WgradSplit& sp) {
+  dim3 grid(a.KO / 128, (unsigned)(a.R * a.S * (a.CI / 128)), sp.nchunks);
+  DISPATCH_16(a.x, T16, {
+    pick<WG_PLAIN, WG_SCALED, WG_KMIN>(mode, [&](auto m) {
+      constexpr WgradMode M_ = decltype(m)::value;
+      launch256(conv_wgrad_mfma_t128<T16, M_ == WG_SCALED, M_ == WG_KMIN>,
+                grid, 0, (const T16*)a.x.data_ptr(),
+                (const T16*)a.dy.data_ptr(), a.asc, a.ash,
+                sp.part.data_ptr<float>(), a.N, a.Hi, a.Wi, a.CI, a.KO, a.Ho,
+                a.Wo, a.R, a.S, a.stride, a.pad, sp.m_per_chunk, sp.nchunks);
+    });
+  });
+}
+
+void wgrad_tap_launch(const WgradArgs& a, int KT, WgradMode mode,
+                      const WgradSplit& sp) {
+  dim3 grid(a.KO / KT, a.R * a.S * (a.CI / 64), sp.nchunks);
+  DISPATCH_16(a.x, T16, {
+    pick<128, 64>(KT, [&](auto kt) {
+      pick<WG_PLAIN, WG_SCALED, WG_KMIN>(mode, [&](auto m) {
+        constexpr WgradMode M_ = decltype(m)::value;
+        launch256(conv_wgrad_mfma_kernel<T16, decltype(kt)::value,
+                                         M_ == WG_SCALED, M_ == WG_KMIN>,
+                  grid, 0, (const T16*)a.x.data_ptr(),
+                  (const T16*)a.dy.data_ptr(), a.asc, a.ash,
+                  sp.part.data_ptr<float>(), a.N, a.Hi, a.Wi, a.CI, a.KO,
+                  a.Ho, a.Wo, a.R, a.S, a.stride, a.pad, sp.m_per_chunk,
+                  sp.nchunks);
+      });
+    });
+  });
+}
+
+}  // namespace
 
 // asc/ash (optional): lazy-BN transform on the x operand (see fwd launcher)
 void conv_wgrad_mfma_launch(at::Tensor x, at::Tensor dy, at::Tensor dw,
                             long R, long S, long stride, long pad,
                             at::Tensor asc, at::Tensor ash) {
-  const float* asc_p = asc.defined() && asc.numel() ? asc.data_ptr<float>()
-                                                    : nullptr;
-  const float* ash_p = ash.defined() && ash.numel() ? ash.data_ptr<float>()
-                                                    : nullptr;
-  const int N = x.size(0), Hi = x.size(1), Wi = x.size(2), CI = x.size(3);
-  const int Ho = dy.size(1), Wo = dy.size(2), KO = dy.size(3);
-  const long M = (long)N * Ho * Wo;
-  // 3x3/s1/p1 with power-of-two W (8..64): all-taps halo kernel.
-  // Measured SLOWER than the tap-per-block kernel (413 vs ~280 us avg:
-  // v236 VGPRs -> 2 waves/SIMD, and the 8-scalar-u16 b-fragment gather is
-  // LDS/VALU-bound) — kept behind MI355X_WGRAD_HALO=1 for further work.
-  static const bool halo_on = [] {
-    const char* e = getenv("MI355X_WGRAD_HALO");
-    return e && e[0] == '1';
-  }();
-  const bool halo = halo_on && !asc_p && R == 3 && S == 3 && stride == 1 && pad == 1 &&
-                    Hi == Ho && Wi == Wo && Wo >= 8 && Wo <= 64 &&
-                    (Wo & (Wo - 1)) == 0 && ((long)Ho * Wo) % 64 == 0;
-  if (halo) {
-    int wshift = 0;
-    while ((1 << wshift) < Wo) ++wshift;
-    const long blocks_xy = (KO / 64) * (CI / 64);
-    long nchunks = std::min<long>(std::max<long>(512 / blocks_xy, 1),
-                                  cdiv_l(M, 64));
-    long m_per_chunk = cdiv_l(cdiv_l(M, nchunks), 64) * 64;
-    nchunks = cdiv_l(M, m_per_chunk);
-    const long E = (long)KO * CI * 9;
-    at::Tensor part =
-        nchunks > 1 ? at::empty({nchunks, E}, dw.options()) : dw;
-    dim3 grid(KO / 64, CI / 64, (unsigned)nchunks);
-    DISPATCH_16(x, T16, {
-      hipLaunchKernelGGL(conv_wgrad_halo3<T16>, grid, dim3(256), 0,
-                         cur_stream(), (const T16*)x.data_ptr(),
-                         (const T16*)dy.data_ptr(), part.data_ptr<float>(),
-                         N, Hi, Wi, CI, KO, wshift, m_per_chunk);
-    });
-    if (nchunks > 1) wgrad_reduce_launch(part, dw, E, nchunks);
-    return;
-  }
+  const float* asc_p = f32_or_null(asc);
+  const WgradArgs a{x, dy, asc_p, asc_p ? f32_or_null(ash) : nullptr,
+                    (int)x.size(0), (int)x.size(1), (int)x.size(2),
+                    (int)x.size(3), (int)dy.size(3), (int)dy.size(1),
+                    (int)dy.size(2), (int)R, (int)S, (int)stride, (int)pad};
+  const long M = (long)a.N * a.Ho * a.Wo;
+  const long E = (long)a.KO * R * S * a.CI;
   // 3x3/s1/p1: s-grouped kernel (3 taps per stage) — MI355X_WGRAD_S3=0
   // falls back to the tap-per-block kernel
-  static const bool s3_on = [] {
-    const char* e = getenv("MI355X_WGRAD_S3");
-    return !e || e[0] != '0';
-  }();
-  if (s3_on && R == 3 && S == 3 && stride == 1 && pad == 1 && Hi == Ho &&
-      Wi == Wo) {
-    static const long cap3 = [] {
-      const char* e = getenv("MI355X_WGRAD_CHUNKS");
-      return e ? atol(e) : 0L;
-    }();
-    int nchunks = (int)std::max<long>(std::min<long>(cdiv_l(M, 4096), 4096),
-                                      1);
-    if (cap3 > 0) nchunks = (int)std::min<long>(nchunks, cap3);
-    long m_per_chunk = cdiv_l(cdiv_l(M, nchunks), WGM) * WGM;
-    nchunks = (int)cdiv_l(M, m_per_chunk);
-    static const long ktf = [] {  // A/B knob (r18: KT=64 90.98k vs
-      const char* e = getenv("MI355X_WGRAD_S3_KT");  // KT=128 87.9k img/s)
-      return e ? atol(e) : 0L;
-    }();
-    // KT=64 default even when KO%128==0: occupancy 3 vs 2 outweighs the
-    // wider tile's staging amortization (measured +3.4% whole-bench)
+  static const bool s3_on = EnvKnob("MI355X_WGRAD_S3").on();
+  if (s3_on && R == 3 && S == 3 && stride == 1 && pad == 1 && a.Hi == a.Ho &&
+      a.Wi == a.Wo) {
+    // A/B knob (r18: KT=64 90.98k vs KT=128 87.9k img/s). KT=64 default
+    // even when KO%128==0: occupancy 3 vs 2 outweighs the wider tile's
+    // staging amortization (measured +3.4% whole-bench)
+    static const long ktf = EnvKnob("MI355X_WGRAD_S3_KT").num(0);
+    // default ON (+0.5% r18, interleaved A/B x2); =0 disables
+    static const bool kminor = EnvKnob("MI355X_S3_KMINOR").on();
     const int KT = (ktf == 128 && !asc_p) ? 128 : 64;  // scaled: KT=64 only
-    dim3 grid(KO / KT, 3 * (CI / 64), nchunks);
-    const long E = (long)KO * 9 * CI;
-    at::Tensor part = nchunks > 1
-                          ? at::empty({nchunks, E}, dw.options())
-                          : dw;
-    static const bool kminor = [] {  // default ON (+0.5% r18, interleaved
-      const char* e = getenv("MI355X_S3_KMINOR");  // A/B x2); =0 disables
-      return !e || e[0] != '0';
-    }();
-    DISPATCH_16(x, T16, {
-      if (KT == 128)
-        hipLaunchKernelGGL((conv_wgrad_mfma_s3<T16, 128>), grid, dim3(256),
-                           0, cur_stream(), (const T16*)x.data_ptr(),
-                           (const T16*)dy.data_ptr(), nullptr, nullptr,
-                           part.data_ptr<float>(),
-                           N, Hi, Wi, CI, KO, Ho, Wo, m_per_chunk, nchunks);
-      else if (kminor && !asc_p)
-        hipLaunchKernelGGL((conv_wgrad_mfma_s3<T16, 64, false, true>), grid,
-                           dim3(256), 0, cur_stream(),
-                           (const T16*)x.data_ptr(),
-                           (const T16*)dy.data_ptr(), nullptr, nullptr,
-                           part.data_ptr<float>(),
-                           N, Hi, Wi, CI, KO, Ho, Wo, m_per_chunk, nchunks);
-      else if (asc_p)
-        hipLaunchKernelGGL((conv_wgrad_mfma_s3<T16, 64, true>), grid,
-                           dim3(256), 0, cur_stream(),
-                           (const T16*)x.data_ptr(),
-                           (const T16*)dy.data_ptr(), asc_p, ash_p,
-                           part.data_ptr<float>(),
-                           N, Hi, Wi, CI, KO, Ho, Wo, m_per_chunk, nchunks);
-      else
-        hipLaunchKernelGGL((conv_wgrad_mfma_s3<T16, 64>), grid, dim3(256),
-                           0, cur_stream(), (const T16*)x.data_ptr(),
-                           (const T16*)dy.data_ptr(), nullptr, nullptr,
-                           part.data_ptr<float>(),
-                           N, Hi, Wi, CI, KO, Ho, Wo, m_per_chunk, nchunks);
-    });
-    if (nchunks > 1) wgrad_reduce_launch(part, dw, E, nchunks);
+    const WgradSplit sp = wgrad_split(M, E, dw, wgrad_chunk_cap());
+    wgrad_s3_launch(a, KT, wgrad_mode(a, kminor), sp);
+    wgrad_split_finish(sp, dw);
     return;
   }
   // KO%128 && CI%128 (notably every r50 1x1 bottleneck conv): 128x128
   // output tile, 4 acc tiles per wave — 2x the MFMA per staged byte of
   // the 64-wide-CI kernel (which measured ~283 TF on these shapes)
-  static const bool t128_on = [] {
-    const char* e = getenv("MI355X_WGRAD_T128");
-    return !e || e[0] != '0';
-  }();
-  if (t128_on && KO % 128 == 0 && CI % 128 == 0) {
-    int nchunks = (int)std::max<long>(std::min<long>(cdiv_l(M, 4096), 4096),
-                                      1);
-    long m_per_chunk = cdiv_l(cdiv_l(M, nchunks), WGM) * WGM;
-    nchunks = (int)cdiv_l(M, m_per_chunk);
-    dim3 grid(KO / 128, (unsigned)(R * S * (CI / 128)), nchunks);
-    const long E = (long)KO * R * S * CI;
-    at::Tensor part = nchunks > 1
-                          ? at::empty({nchunks, E}, dw.options())
-                          : dw;
-    static const bool kmin128 = [] {  // default ON (+0.8% r50,
-      const char* e = getenv("MI355X_T128_KMINOR");  // interleaved A/B x2)
-      return !e || e[0] != '0';
-    }();
-    DISPATCH_16(x, T16, {
-      if (asc_p)
-        hipLaunchKernelGGL((conv_wgrad_mfma_t128<T16, true>), grid,
-                           dim3(256), 0, cur_stream(),
-                           (const T16*)x.data_ptr(),
-                           (const T16*)dy.data_ptr(), asc_p, ash_p,
-                           part.data_ptr<float>(),
-                           N, Hi, Wi, CI, KO, Ho, Wo, (int)R, (int)S,
-                           (int)stride, (int)pad, m_per_chunk, nchunks);
-      else if (kmin128)
-        hipLaunchKernelGGL((conv_wgrad_mfma_t128<T16, false, true>), grid,
-                           dim3(256), 0, cur_stream(),
-                           (const T16*)x.data_ptr(),
-                           (const T16*)dy.data_ptr(), nullptr, nullptr,
-                           part.data_ptr<float>(),
-                           N, Hi, Wi, CI, KO, Ho, Wo, (int)R, (int)S,
-                           (int)stride, (int)pad, m_per_chunk, nchunks);
-      else
-        hipLaunchKernelGGL((conv_wgrad_mfma_t128<T16>), grid, dim3(256), 0,
-                           cur_stream(), (const T16*)x.data_ptr(),
-                           (const T16*)dy.data_ptr(), nullptr, nullptr,
-                           part.data_ptr<float>(),
-                           N, Hi, Wi, CI, KO, Ho, Wo, (int)R, (int)S,
-                           (int)stride, (int)pad, m_per_chunk, nchunks);
-    });
-    if (nchunks > 1) wgrad_reduce_launch(part, dw, E, nchunks);
+  static const bool t128_on = EnvKnob("MI355X_WGRAD_T128").on();
+  if (t128_on && a.KO % 128 == 0 && a.CI % 128 == 0) {
+    // default ON (+0.8% r50, interleaved A/B x2)
+    static const bool kmin128 = EnvKnob("MI355X_T128_KMINOR").on();
+    const WgradSplit sp = wgrad_split(M, E, dw, 0);
+    wgrad_t128_launch(a, wgrad_mode(a, kmin128), sp);
+    wgrad_split_finish(sp, dw);
     return;
   }
-  const long blocks_xy = (KO / 64) * (R * S * (CI / 64));
-  static const long cap = [] {  // ablation knob: MI355X_WGRAD_CHUNKS
-    const char* e = getenv("MI355X_WGRAD_CHUNKS");
-    return e ? atol(e) : 0L;
-  }();
-  // A/B on layer1 b256 (partial slabs): m/chunk 1216 -> 189us, 4096 ->
-  // 137us, 16384 -> 327us: the lever is PER-CHUNK depth (~4096 m), which
-  // also holds as M grows with batch (576-total-blocks regressed b1024)
-  int nchunks = (int)std::max<long>(
-      std::min<long>(cdiv_l(M, 4096), 4096), 1);
-  if (cap > 0) nchunks = (int)std::min<long>(nchunks, cap);
-  nchunks = std::max(nchunks, 1);
-  long m_per_chunk = cdiv_l(cdiv_l(M, nchunks), WGM) * WGM;
-  nchunks = (int)cdiv_l(M, m_per_chunk);
-  const int KT = KO % 128 == 0 ? 128 : 64;
-  dim3 grid(KO / KT, R * S * (CI / 64), nchunks);
-  const long E = (long)KO * R * S * CI;
-  at::Tensor part = nchunks > 1
-                        ? at::empty({nchunks, E}, dw.options())
-                        : dw;
-  static const bool kming = [] {  // shares the s3 knob family
-    const char* e = getenv("MI355X_WGRAD_KMINOR");
-    return !e || e[0] != '0';
-  }();
-  DISPATCH_16(x, T16, {
-    if (KT == 128) {
-      if (asc_p)
-        hipLaunchKernelGGL((conv_wgrad_mfma_kernel<T16, 128, true>), grid,
-                           dim3(256), 0, cur_stream(),
-                           (const T16*)x.data_ptr(),
-                           (const T16*)dy.data_ptr(), asc_p, ash_p,
-                           part.data_ptr<float>(),
-                           N, Hi, Wi, CI, KO, Ho, Wo, (int)R, (int)S,
-                           (int)stride, (int)pad, m_per_chunk, nchunks);
-      else if (kming)
-        hipLaunchKernelGGL((conv_wgrad_mfma_kernel<T16, 128, false, true>),
-                           grid, dim3(256), 0, cur_stream(),
-                           (const T16*)x.data_ptr(),
-                           (const T16*)dy.data_ptr(), nullptr, nullptr,
-                           part.data_ptr<float>(),
-                           N, Hi, Wi, CI, KO, Ho, Wo, (int)R, (int)S,
-                           (int)stride, (int)pad, m_per_chunk, nchunks);
-      else
-        hipLaunchKernelGGL((conv_wgrad_mfma_kernel<T16, 128>), grid,
-                           dim3(256), 0, cur_stream(),
-                           (const T16*)x.data_ptr(),
-                           (const T16*)dy.data_ptr(), nullptr, nullptr,
-                           part.data_ptr<float>(),
-                           N, Hi, Wi, CI, KO, Ho, Wo, (int)R, (int)S,
-                           (int)stride, (int)pad, m_per_chunk, nchunks);
-    } else {
-      if (asc_p)
-        hipLaunchKernelGGL((conv_wgrad_mfma_kernel<T16, 64, true>), grid,
-                           dim3(256), 0, cur_stream(),
-                           (const T16*)x.data_ptr(),
-                           (const T16*)dy.data_ptr(), asc_p, ash_p,
-                           part.data_ptr<float>(),
-                           N, Hi, Wi, CI, KO, Ho, Wo, (int)R, (int)S,
-                           (int)stride, (int)pad, m_per_chunk, nchunks);
-      else if (kming)
-        hipLaunchKernelGGL((conv_wgrad_mfma_kernel<T16, 64, false, true>),
-                           grid, dim3(256), 0, cur_stream(),
-                           (const T16*)x.data_ptr(),
-                           (const T16*)dy.data_ptr(), nullptr, nullptr,
-                           part.data_ptr<float>(),
-                           N, Hi, Wi, CI, KO, Ho, Wo, (int)R, (int)S,
-                           (int)stride, (int)pad, m_per_chunk, nchunks);
-      else
-        hipLaunchKernelGGL((conv_wgrad_mfma_kernel<T16, 64>), grid,
-                           dim3(256), 0, cur_stream(),
-                           (const T16*)x.data_ptr(),
-                           (const T16*)dy.data_ptr(), nullptr, nullptr,
-                           part.data_ptr<float>(),
-                           N, Hi, Wi, CI, KO, Ho, Wo, (int)R, (int)S,
-                           (int)stride, (int)pad, m_per_chunk, nchunks);
-    }
-  });
-  if (nchunks > 1) wgrad_reduce_launch(part, dw, E, nchunks);
+  static const bool kming = EnvKnob("MI355X_WGRAD_KMINOR").on();
+  const WgradSplit sp = wgrad_split(M, E, dw, wgrad_chunk_cap());
+  wgrad_tap_launch(a, a.KO % 128 == 0 ? 128 : 64, wgrad_mode(a, kming), sp);
+  wgrad_split_finish(sp, dw);
 }
+
+namespace {
+
+// ---- fwd / dgrad ------------------------------------------------------
+// conv_gather_gemm, all three uses: fwd (plain or SCALED), GENC fwd
+// (NT=2 only) and dgrad (TRANS, plain or ADDIN). in/out are the GEMM's
+// A-side and result tensors: (x, y) for fwd, (dy, dx) for dgrad.
+// stats (optional, [2,KO], fully overwritten): the epilogue emits per-block
+// (sum,sumsq) partials to a slab and stats_slab_reduce folds them.
+void gather_gemm_launch(bool trans, bool genc, const at::Tensor& in,
+                        const at::Tensor& wgt, const at::Tensor& bias,
+                        const at::Tensor& addin, const float* asc,
+                        const float* ash, at::Tensor& out,
+                        const at::Tensor& stats, long R, long S, long stride,
+                        long pad, long b_row_stride, long b_rs_stride,
+                        long act) {
+  const int N = in.size(0), Hi = in.size(1), Wi = in.size(2), CI = in.size(3);
+  const int Ho = out.size(1), Wo = out.size(2), KO = out.size(3);
+  const long M = (long)N * Ho * Wo;
+  // BN=128 halves barriers per MFMA but also halves the grid — only use
+  // it when M is large enough to keep the chip full at BM=128 tiles
+  const bool wide =
+      !genc && KO % 128 == 0 && cdiv_l(M, BM) * (KO / 128) >= 1024;
+  const int nt = wide ? 4 : 2;
+  dim3 grid((unsigned)cdiv_l(M, BM), KO / (nt * 32));
+  at::Tensor zp = conv_zero_page(in);
+  at::Tensor slab;
+  if (present(stats))
+    slab = at::empty({(long)grid.y * grid.x * 2 * nt * 32},
+                     in.options().dtype(at::kFloat));
+  DISPATCH_16(in, T16, {
+    auto go = [&](auto kern) {
+      launch256(kern, grid, 0, (const T16*)in.data_ptr(),
+                (const T16*)wgt.data_ptr(), f32_or_null(bias),
+                (const T16*)zp.data_ptr(),
+                present(addin) ? (const T16*)addin.data_ptr() : nullptr, asc,
+                ash, (T16*)out.data_ptr(), f32_or_null(slab), N, Hi, Wi, CI,
+                KO, Ho, Wo, R, S, stride, pad, b_row_stride, b_rs_stride, act,
+                present(bias));
+    };
+    if (genc)
+      go(conv_gather_gemm<T16, false, true, 2>);
+    else
+      pick<4, 2>(nt, [&](auto NT) {
+        if (trans)
+          pick<true, false>(present(addin), [&](auto ADDIN) {
+            go(conv_gather_gemm<T16, true, false, decltype(NT)::value,
+                                decltype(ADDIN)::value>);
+          });
+        else
+          pick<true, false>(asc != nullptr, [&](auto SCALED) {
+            go(conv_gather_gemm<T16, false, false, decltype(NT)::value, false,
+                                decltype(SCALED)::value>);
+          });
+      });
+  });
+  if (slab.defined()) stats_slab_reduce(slab, stats, grid.x, 2 * nt * 32, KO);
+}
+
+// LDS geometry of conv_patch_gemm for image width W: NR patch rows and the
+// dynamic LDS bytes. NR = rows spanned by a 128-output tile starting
+// mid-row, +2 halo rows: 128/W+3 was ONE short for W in {56,28,14,7} (tap
+// r=2 then read past the patch -> diverging ResNet-50 training)
+struct PatchGeom {
+  int NR;
+  size_t smem;
+};
+PatchGeom patch_geom(int W) {
+  const int NR = (W + 126) / W + 3;
+  return {NR, ((size_t)NR * (W + 2) * PCS + PCS + 64 * LDK) * 2};
+}
+
+// conv_patch_gemm (3x3/s1/p1, W <= 64): fwd (plain or SCALED, optional
+// stats) and dgrad (TRANS, plain or ADDIN); in/out as in gather_gemm_launch
+void patch_gemm_launch(bool trans, const at::Tensor& in,
+                       const at::Tensor& wgt, const at::Tensor& bias,
+                       const at::Tensor& addin, const float* asc,
+                       const float* ash, at::Tensor& out,
+                       const at::Tensor& stats, long b_row_stride,
+                       long b_rs_stride, long act) {
+  const int N = in.size(0), Hi = in.size(1), Wi = in.size(2), CI = in.size(3);
+  const int KO = out.size(3);
+  const long M = (long)N * Hi * Wi;
+  const PatchGeom pg = patch_geom(Wi);
+  dim3 grid((unsigned)cdiv_l(M, 128), KO / 64);
+  at::Tensor slab;
+  if (present(stats))
+    slab = at::empty({(long)grid.y * grid.x * 128},
+                     in.options().dtype(at::kFloat));
+  DISPATCH_16(in, T16, {
+    auto go = [&](auto kern) {
+      launch256(kern, grid, pg.smem, (const T16*)in.data_ptr(),
+                (const T16*)wgt.data_ptr(), f32_or_null(bias),
+                present(addin) ? (const T16*)addin.data_ptr() : nullptr, asc,
+                ash, (T16*)out.data_ptr(), f32_or_null(slab), N, Hi, Wi, CI,
+                KO, b_row_stride, b_rs_stride, act, present(bias), pg.NR);
+    };
+    if (trans)
+      pick<true, false>(present(addin), [&](auto ADDIN) {
+        go(conv_patch_gemm<T16, true, decltype(ADDIN)::value>);
+      });
+    else
+      pick<true, false>(asc != nullptr, [&](auto SCALED) {
+        go(conv_patch_gemm<T16, false, false, decltype(SCALED)::value>);
+      });
+  });
+  if (slab.defined()) stats_slab_reduce(slab, stats, grid.x, 128, KO);
+}
+
+// conv_dgrad_s2_gemm: the 4 parity classes ride in blockIdx.z
+void dgrad_s2_launch(const at::Tensor& dy, const at::Tensor& wflip,
+                     at::Tensor& dx, const at::Tensor& addin, long R, long S,
+                     long pad) {
+  const int N = dy.size(0), P = dy.size(1), Q = dy.size(2), KO = dy.size(3);
+  const int H = dx.size(1), W = dx.size(2), CI = dx.size(3);
+  const long Mmax = (long)N * ((H + 1) / 2) * ((W + 1) / 2);
+  const bool wide = CI % 128 == 0 && cdiv_l(Mmax, BM) * (CI / 128) * 4 >= 1024;
+  const int nt = wide ? 4 : 2;
+  dim3 grid((unsigned)cdiv_l(Mmax, BM), CI / (nt * 32), 4);
+  at::Tensor zp = conv_zero_page(dy);
+  DISPATCH_16(dy, T16, {
+    pick<4, 2>(nt, [&](auto NT) {
+      pick<true, false>(present(addin), [&](auto ADDIN) {
+        launch256(conv_dgrad_s2_gemm<T16, decltype(NT)::value,
+                                     decltype(ADDIN)::value>,
+                  grid, 0, (const T16*)dy.data_ptr(),
+                  (const T16*)wflip.data_ptr(), (const T16*)zp.data_ptr(),
+                  present(addin) ? (const T16*)addin.data_ptr() : nullptr,
+                  (T16*)dx.data_ptr(), N, P, Q, KO, CI, H, W, R, S, pad);
+      });
+    });
+  });
+}
+
+}  // namespace
 
 // GENC fwd: wpad = [KO, KGP] zero-padded (cast_permute_krsc_pad)
 void conv_fwd_mfma_genc_launch(at::Tensor x, at::Tensor wpad, at::Tensor bias,
                                at::Tensor y, long R, long S, long stride,
                                long pad, long act) {
-  const int N = x.size(0), Hi = x.size(1), Wi = x.size(2), CI = x.size(3);
-  const int KO = wpad.size(0);
-  const long KGP = wpad.size(1);
-  const int Ho = y.size(1), Wo = y.size(2);
-  const long M = (long)N * Ho * Wo;
-  dim3 grid((unsigned)cdiv_l(M, BM), KO / BN);
-  const int has_bias = bias.numel() > 0;
-  at::Tensor zp = conv_zero_page(x);
-  DISPATCH_16(x, T16, {
-    hipLaunchKernelGGL((conv_gather_gemm<T16, false, true, 2>), grid,
-                       dim3(256), 0, cur_stream(), (const T16*)x.data_ptr(),
-                       (const T16*)wpad.data_ptr(),
-                       has_bias ? bias.data_ptr<float>() : nullptr,
-                       (const T16*)zp.data_ptr(), nullptr, nullptr,
-                       nullptr,
-                       (T16*)y.data_ptr(), nullptr, N, Hi, Wi, CI, KO, Ho,
-                       Wo, (int)R, (int)S, (int)stride, (int)pad, KGP, 0,
-                       (int)act, has_bias);
-  });
+  gather_gemm_launch(false, true, x, wpad, bias, at::Tensor(), nullptr,
+                     nullptr, y, at::Tensor(), R, S, stride, pad,
+                     wpad.size(1), 0, act);
 }
 
 // fwd: in = x[N,Hi,Wi,CI], wgt = w16 [KO, R,S,CI] row-major.
-// stats (optional, [2,C], fully overwritten): conv->BN fusion — the epilogue emits
-// per-block (sum,sumsq) partials to a slab and conv_stats_reduce folds
-// them, replacing BN's separate full-tensor bn_stats pass.
+// stats (optional, [2,C], fully overwritten): conv->BN fusion — replaces
+// BN's separate full-tensor bn_stats pass.
 // asc/ash (optional [CI] fp32): lazy-BN A-side transform — the x operand
 // is normalized+ReLU'd on load (z = relu(x*asc+ash)); the BN apply pass
 // and its output tensor disappear.
 void conv_fwd_mfma_launch(at::Tensor x, at::Tensor w, at::Tensor bias,
                           at::Tensor y, long stride, long pad, long act,
                           at::Tensor stats, at::Tensor asc, at::Tensor ash) {
-  const float* asc_p = asc.defined() && asc.numel() ? asc.data_ptr<float>()
-                                                    : nullptr;
-  const float* ash_p = ash.defined() && ash.numel() ? ash.data_ptr<float>()
-                                                    : nullptr;
-  const int N = x.size(0), Hi = x.size(1), Wi = x.size(2), CI = x.size(3);
-  const int KO = w.size(0), R = w.size(1), S = w.size(2);
-  const int Ho = y.size(1), Wo = y.size(2);
-  const long M = (long)N * Ho * Wo;
-  const int has_bias = bias.numel() > 0;
-  // A/B (b1024 layer shapes): glds 597/685/561 TF vs register staging
-  // 632/692/665 — glds LOSES at this kernel's 5-blocks/CU occupancy, as
-  // the guide's regime gate predicts (pays only at ~1 block/CU, vgpr>200).
-  // Kept behind MI355X_CONV_GLDS=1 as a documented negative result.
-  static const int glds_mode = [] {
-    const char* e = getenv("MI355X_CONV_GLDS");
-    return e ? atoi(e) : 0;
-  }();
-  if (glds_mode && !asc_p && !(stats.defined() && stats.numel() > 0)) {
-    at::Tensor zp = conv_zero_page(x);
-    const bool wide = KO % 128 == 0 && cdiv_l(M, BM) * (KO / 128) >= 1024;
-    dim3 grid((unsigned)cdiv_l(M, BM), KO / (wide ? 128 : 64));
-    DISPATCH_16(x, T16, {
-      if (wide)
-        hipLaunchKernelGGL((conv_fwd_glds<T16, 4>), grid, dim3(256), 0,
-                           cur_stream(), (const T16*)x.data_ptr(),
-                           (const T16*)w.data_ptr(),
-                           has_bias ? bias.data_ptr<float>() : nullptr,
-                           (const T16*)zp.data_ptr(), (T16*)y.data_ptr(), N,
-                           Hi, Wi, CI, KO, Ho, Wo, R, S, (int)stride,
-                           (int)pad, (int)act, has_bias);
-      else
-        hipLaunchKernelGGL((conv_fwd_glds<T16, 2>), grid, dim3(256), 0,
-                           cur_stream(), (const T16*)x.data_ptr(),
-                           (const T16*)w.data_ptr(),
-                           has_bias ? bias.data_ptr<float>() : nullptr,
-                           (const T16*)zp.data_ptr(), (T16*)y.data_ptr(), N,
-                           Hi, Wi, CI, KO, Ho, Wo, R, S, (int)stride,
-                           (int)pad, (int)act, has_bias);
-    });
-    return;
-  }
+  const float* asc_p = f32_or_null(asc);
+  const float* ash_p = asc_p ? f32_or_null(ash) : nullptr;
+  const long Hi = x.size(1), Wi = x.size(2), CI = x.size(3);
+  const long R = w.size(1), S = w.size(2);
   // 3x3/s1/p1 patch kernel: one geometric LDS patch per c-chunk serves
-  // all 9 taps (MI355X_CONV_PATCH=0 falls back to the per-tap gather)
-  static const bool patch_on = [] {
-    const char* e = getenv("MI355X_CONV_PATCH");
-    return !e || e[0] != '0';
-  }();
-  if (patch_on && R == 3 && S == 3 && stride == 1 && pad == 1 && Ho == Hi &&
-      Wo == Wi && Wo <= 64) {
-    // rows spanned by a 128-output tile starting mid-row, +2 halo rows:
-    // 128/Wo+3 was ONE short for Wo in {56,28,14,7} (tap r=2 then read
-    // past the patch -> diverging ResNet-50 training)
-    const int NR = (Wo + 126) / Wo + 3;
-    const size_t smem = ((size_t)NR * (Wi + 2) * PCS + PCS + 64 * LDK) * 2;
-    dim3 pgrid_((unsigned)cdiv_l(M, 128), KO / 64);
-    at::Tensor pslab;
-    float* pslab_ptr = nullptr;
-    if (stats.defined() && stats.numel() > 0) {
-      pslab = at::empty({(long)pgrid_.y * pgrid_.x * 128},
-                        x.options().dtype(at::kFloat));
-      pslab_ptr = pslab.data_ptr<float>();
-    }
-    DISPATCH_16(x, T16, {
-      if (asc_p)
-        hipLaunchKernelGGL((conv_patch_gemm<T16, false, false, true>),
-                           pgrid_, dim3(256), smem, cur_stream(),
-                           (const T16*)x.data_ptr(), (const T16*)w.data_ptr(),
-                           has_bias ? bias.data_ptr<float>() : nullptr,
-                           nullptr, asc_p, ash_p, (T16*)y.data_ptr(),
-                           pslab_ptr, N, Hi, Wi, CI, KO, (long)R * S * CI,
-                           (long)CI, (int)act, has_bias, NR);
-      else
-        hipLaunchKernelGGL((conv_patch_gemm<T16, false>), pgrid_, dim3(256),
-                           smem, cur_stream(), (const T16*)x.data_ptr(),
-                           (const T16*)w.data_ptr(),
-                           has_bias ? bias.data_ptr<float>() : nullptr,
-                           nullptr, nullptr, nullptr, (T16*)y.data_ptr(),
-                           pslab_ptr, N, Hi, Wi, CI, KO, (long)R * S * CI,
-                           (long)CI, (int)act, has_bias, NR);
-    });
-    if (pslab_ptr)
-      stats_slab_reduce(pslab, stats, pgrid_.x, 128, KO);
+  // all 9 taps
+  if (conv_patch_on() && R == 3 && S == 3 && stride == 1 && pad == 1 &&
+      y.size(1) == Hi && y.size(2) == Wi && Wi <= 64) {
+    patch_gemm_launch(false, x, w, bias, at::Tensor(), asc_p, ash_p, y, stats,
+                      R * S * CI, CI, act);
     return;
   }
-  // BN=128 halves barriers per MFMA but also halves the grid — only use
-  // it when M is large enough to keep the chip full at BM=128 tiles
-  const bool wide = KO % 128 == 0 && cdiv_l(M, BM) * (KO / 128) >= 1024;
-  dim3 grid((unsigned)cdiv_l(M, BM), KO / (wide ? 128 : 64));
-  at::Tensor zp2 = conv_zero_page(x);
-  const int bnt2 = 2 * (wide ? 128 : 64);
-  at::Tensor slab;
-  float* stats_slab_ptr = nullptr;
-  if (stats.defined() && stats.numel() > 0) {
-    slab = at::empty({(long)grid.y * grid.x * bnt2},
-                     x.options().dtype(at::kFloat));
-    stats_slab_ptr = slab.data_ptr<float>();
-  }
-  DISPATCH_16(x, T16, {
-    if (wide) {
-      if (asc_p)
-        hipLaunchKernelGGL((conv_gather_gemm<T16, false, false, 4, false,
-                                             true>),
-                           grid, dim3(256), 0, cur_stream(),
-                           (const T16*)x.data_ptr(), (const T16*)w.data_ptr(),
-                           has_bias ? bias.data_ptr<float>() : nullptr,
-                           (const T16*)zp2.data_ptr(), nullptr, asc_p, ash_p,
-                           (T16*)y.data_ptr(), stats_slab_ptr, N, Hi, Wi, CI,
-                           KO, Ho, Wo, R, S, (int)stride, (int)pad,
-                           (long)R * S * CI, (long)CI, (int)act, has_bias);
-      else
-        hipLaunchKernelGGL((conv_gather_gemm<T16, false, false, 4>), grid,
-                           dim3(256), 0, cur_stream(),
-                           (const T16*)x.data_ptr(), (const T16*)w.data_ptr(),
-                           has_bias ? bias.data_ptr<float>() : nullptr,
-                           (const T16*)zp2.data_ptr(), nullptr, nullptr,
-                           nullptr,
-                           (T16*)y.data_ptr(), stats_slab_ptr, N, Hi, Wi, CI,
-                           KO, Ho, Wo, R, S, (int)stride, (int)pad,
-                           (long)R * S * CI, (long)CI, (int)act, has_bias);
-    } else {
-      if (asc_p)
-        hipLaunchKernelGGL((conv_gather_gemm<T16, false, false, 2, false,
-                                             true>),
-                           grid, dim3(256), 0, cur_stream(),
-                           (const T16*)x.data_ptr(), (const T16*)w.data_ptr(),
-                           has_bias ? bias.data_ptr<float>() : nullptr,
-                           (const T16*)zp2.data_ptr(), nullptr, asc_p, ash_p,
-                           (T16*)y.data_ptr(), stats_slab_ptr, N, Hi, Wi, CI,
-                           KO, Ho, Wo, R, S, (int)stride, (int)pad,
-                           (long)R * S * CI, (long)CI, (int)act, has_bias);
-      else
-        hipLaunchKernelGGL((conv_gather_gemm<T16, false, false, 2>), grid,
-                           dim3(256), 0, cur_stream(),
-                           (const T16*)x.data_ptr(), (const T16*)w.data_ptr(),
-                           has_bias ? bias.data_ptr<float>() : nullptr,
-                           (const T16*)zp2.data_ptr(), nullptr, nullptr,
-                           nullptr,
-                           (T16*)y.data_ptr(), stats_slab_ptr, N, Hi, Wi, CI,
-                           KO, Ho, Wo, R, S, (int)stride, (int)pad,
-                           (long)R * S * CI, (long)CI, (int)act, has_bias);
-    }
-  });
-  if (stats_slab_ptr)
-    stats_slab_reduce(slab, stats, grid.x, bnt2, KO);
+  gather_gemm_launch(false, false, x, w, bias, at::Tensor(), asc_p, ash_p, y,
+                     stats, R, S, stride, pad, R * S * CI, CI, act);
 }
 
 // dgrad: in = dy[N,P,Q,KO], wflip = [R,S,CI,KO] (w[k,R-1-r,S-1-s,c]),
@@ -2178,136 +1793,23 @@ void conv_fwd_mfma_launch(at::Tensor x, at::Tensor w, at::Tensor bias,
 void conv_dgrad_mfma_launch(at::Tensor dy, at::Tensor wflip, at::Tensor dx,
                             long R, long S, long stride, long pad,
                             at::Tensor addin) {
-  const int N = dy.size(0), P = dy.size(1), Q = dy.size(2), KO = dy.size(3);
-  const int H = dx.size(1), W = dx.size(2), CI = dx.size(3);
-  const long M = (long)N * H * W;
-  const bool has_add = addin.defined() && addin.numel() > 0;
+  const long KO = dy.size(3), CI = dx.size(3);
   // stride-2: parity-specialized kernel (4 classes in blockIdx.z), ~2.6x
   // fewer k-steps for 3x3/s2 and 4x for the 1x1 downsamples
-  static const bool s2_on = [] {
-    const char* e = getenv("MI355X_DGRAD_S2");
-    return !e || e[0] != '0';
-  }();
+  static const bool s2_on = EnvKnob("MI355X_DGRAD_S2").on();
   if (s2_on && stride == 2 && pad <= 8) {
-    const long Mmax = (long)N * ((H + 1) / 2) * ((W + 1) / 2);
-    const bool wide =
-        CI % 128 == 0 && cdiv_l(Mmax, BM) * (CI / 128) * 4 >= 1024;
-    const int BNTs = wide ? 128 : 64;
-    dim3 grid((unsigned)cdiv_l(Mmax, BM), CI / BNTs, 4);
-    at::Tensor zp = conv_zero_page(dy);
-    DISPATCH_16(dy, T16, {
-      const T16* add_p = has_add ? (const T16*)addin.data_ptr() : nullptr;
-      if (wide) {
-        if (has_add)
-          hipLaunchKernelGGL((conv_dgrad_s2_gemm<T16, 4, true>), grid,
-                             dim3(256), 0, cur_stream(),
-                             (const T16*)dy.data_ptr(),
-                             (const T16*)wflip.data_ptr(),
-                             (const T16*)zp.data_ptr(), add_p,
-                             (T16*)dx.data_ptr(), N, P, Q, KO, CI, H, W,
-                             (int)R, (int)S, (int)pad);
-        else
-          hipLaunchKernelGGL((conv_dgrad_s2_gemm<T16, 4>), grid, dim3(256),
-                             0, cur_stream(), (const T16*)dy.data_ptr(),
-                             (const T16*)wflip.data_ptr(),
-                             (const T16*)zp.data_ptr(), nullptr,
-                             (T16*)dx.data_ptr(), N, P, Q, KO, CI, H, W,
-                             (int)R, (int)S, (int)pad);
-      } else {
-        if (has_add)
-          hipLaunchKernelGGL((conv_dgrad_s2_gemm<T16, 2, true>), grid,
-                             dim3(256), 0, cur_stream(),
-                             (const T16*)dy.data_ptr(),
-                             (const T16*)wflip.data_ptr(),
-                             (const T16*)zp.data_ptr(), add_p,
-                             (T16*)dx.data_ptr(), N, P, Q, KO, CI, H, W,
-                             (int)R, (int)S, (int)pad);
-        else
-          hipLaunchKernelGGL((conv_dgrad_s2_gemm<T16, 2>), grid, dim3(256),
-                             0, cur_stream(), (const T16*)dy.data_ptr(),
-                             (const T16*)wflip.data_ptr(),
-                             (const T16*)zp.data_ptr(), nullptr,
-                             (T16*)dx.data_ptr(), N, P, Q, KO, CI, H, W,
-                             (int)R, (int)S, (int)pad);
-      }
-    });
+    dgrad_s2_launch(dy, wflip, dx, addin, R, S, pad);
     return;
   }
-  static const bool patch_on = [] {
-    const char* e = getenv("MI355X_CONV_PATCH");
-    return !e || e[0] != '0';
-  }();
-  if (patch_on && R == 3 && S == 3 && stride == 1 && pad == 1 && P == H &&
-      Q == W && W <= 64) {
-    const int NR = (W + 126) / W + 3;  // see fwd launcher comment
-    const size_t smem = ((size_t)NR * (W + 2) * PCS + PCS + 64 * LDK) * 2;
-    dim3 pgrid_((unsigned)cdiv_l(M, 128), CI / 64);
-    DISPATCH_16(dy, T16, {
-      if (has_add)
-        hipLaunchKernelGGL((conv_patch_gemm<T16, true, true>), pgrid_,
-                           dim3(256), smem, cur_stream(),
-                           (const T16*)dy.data_ptr(),
-                           (const T16*)wflip.data_ptr(), nullptr,
-                           (const T16*)addin.data_ptr(), nullptr, nullptr,
-                           (T16*)dx.data_ptr(), nullptr, N, P, Q, KO, CI,
-                           (long)KO, (long)CI * KO, 0, 0, NR);
-      else
-        hipLaunchKernelGGL((conv_patch_gemm<T16, true>), pgrid_, dim3(256),
-                           smem, cur_stream(), (const T16*)dy.data_ptr(),
-                           (const T16*)wflip.data_ptr(), nullptr, nullptr,
-                           nullptr, nullptr,
-                           (T16*)dx.data_ptr(), nullptr, N, P, Q, KO, CI,
-                           (long)KO, (long)CI * KO, 0, 0, NR);
-    });
+  if (conv_patch_on() && R == 3 && S == 3 && stride == 1 && pad == 1 &&
+      dy.size(1) == dx.size(1) && dy.size(2) == dx.size(2) &&
+      dx.size(2) <= 64) {
+    patch_gemm_launch(true, dy, wflip, at::Tensor(), addin, nullptr, nullptr,
+                      dx, at::Tensor(), KO, CI * KO, 0);
     return;
   }
-  const bool wide = CI % 128 == 0 && cdiv_l(M, BM) * (CI / 128) >= 1024;
-  dim3 grid((unsigned)cdiv_l(M, BM), CI / (wide ? 128 : 64));
-  at::Tensor zp = conv_zero_page(dy);
-  DISPATCH_16(dy, T16, {
-    const T16* add_p = has_add ? (const T16*)addin.data_ptr() : nullptr;
-    if (wide) {
-      if (has_add)
-        hipLaunchKernelGGL((conv_gather_gemm<T16, true, false, 4, true>),
-                           grid, dim3(256), 0, cur_stream(),
-                           (const T16*)dy.data_ptr(),
-                           (const T16*)wflip.data_ptr(), nullptr,
-                           (const T16*)zp.data_ptr(), add_p, nullptr,
-                           nullptr,
-                           (T16*)dx.data_ptr(), nullptr, N, P, Q, KO, CI, H,
-                           W, (int)R, (int)S, (int)stride, (int)pad,
-                           (long)KO, (long)CI * KO, 0, 0);
-      else
-        hipLaunchKernelGGL((conv_gather_gemm<T16, true, false, 4>), grid,
-                           dim3(256), 0, cur_stream(),
-                           (const T16*)dy.data_ptr(),
-                           (const T16*)wflip.data_ptr(), nullptr,
-                           (const T16*)zp.data_ptr(), nullptr, nullptr,
-                           nullptr,
-                           (T16*)dx.data_ptr(), nullptr, N, P, Q, KO, CI, H,
-                           W, (int)R, (int)S, (int)stride, (int)pad,
-                           (long)KO, (long)CI * KO, 0, 0);
-    } else {
-      if (has_add)
-        hipLaunchKernelGGL((conv_gather_gemm<T16, true, false, 2, true>),
-                           grid, dim3(256), 0, cur_stream(),
-                           (const T16*)dy.data_ptr(),
-                           (const T16*)wflip.data_ptr(), nullptr,
-                           (const T16*)zp.data_ptr(), add_p, nullptr,
-                           nullptr,
-                           (T16*)dx.data_ptr(), nullptr, N, P, Q, KO, CI, H,
-                           W, (int)R, (int)S, (int)stride, (int)pad,
-                           (long)KO, (long)CI * KO, 0, 0);
-      else
-        hipLaunchKernelGGL((conv_gather_gemm<T16, true, false, 2>), grid,
-                           dim3(256), 0, cur_stream(),
-                           (const T16*)dy.data_ptr(),
-                           (const T16*)wflip.data_ptr(), nullptr,
-                           (const T16*)zp.data_ptr(), nullptr, nullptr,
-                           nullptr,
-                           (T16*)dx.data_ptr(), nullptr, N, P, Q, KO, CI, H,
-                           W, (int)R, (int)S, (int)stride, (int)pad,
-                           (long)KO, (long)CI * KO, 0, 0);
-    }
-  });
+  gather_gemm_launch(true, false, dy, wflip, at::Tensor(), addin, nullptr,
+                     nullptr, dx, at::Tensor(), R, S, stride, pad, KO,
+                     CI * KO, 0);
 }
+

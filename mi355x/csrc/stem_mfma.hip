@@ -24,7 +24,7 @@
 //   fwd  : y[m, ko]   = sum_kg A_im2col[m, kg] * w24[ko, kg]
 //   wgrad: dw[ko, kg] = sum_m dy[m, ko] * A_im2col[m, kg]
 //          (transposed LDS staging, split-M chunk slabs, wgrad_reduce)
-#include "common.h"
+#include "conv_internal.h"
 
 typedef __attribute__((ext_vector_type(8))) _Float16 half8_s;
 typedef __attribute__((ext_vector_type(16))) float f32x16_s;
@@ -557,8 +557,6 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_stem_gemm(
 
 // host launchers --------------------------------------------------------
 
-at::Tensor conv_zero_page(const at::Tensor& like);  // conv_mfma.hip
-
 // w: [KO, KGP] tap-major padded ([kg = (r*R+s)*3+c]) -> [KO, SKG]
 // row-padded (kg = r*SROW + s*3 + c)
 template <int R_>
@@ -572,9 +570,6 @@ static at::Tensor stem_wpad(const at::Tensor& w) {
                              {0, SKG - R_ * SROW}, 0)
       .contiguous();
 }
-
-void stats_slab_reduce(at::Tensor slab, at::Tensor stats, int gx, int bnt2,
-                       int C);  // conv_mfma.hip
 
 template <int R_, int STRIDE_>
 static bool fwd_stem_gemm_impl(at::Tensor x, at::Tensor w, at::Tensor bias,
@@ -591,10 +586,7 @@ static bool fwd_stem_gemm_impl(at::Tensor x, at::Tensor w, at::Tensor bias,
   const int has_bias = bias.numel() > 0;
   // strip variant (v3) when blocks can't straddle images: the A operand
   // comes from a once-staged LDS strip instead of per-m global gathers
-  static const bool strip_on = [] {
-    const char* e = getenv("MI355X_STEM_STRIP");
-    return !e || e[0] != '0';
-  }();
+  static const bool strip_on = EnvKnob("MI355X_STEM_STRIP").on();
   const long Mimg = (long)Ho * Wo;
   if (strip_on && Mimg % 128 == 0) {
     // rows spanned: 128 outputs cover <= ceil(127/Wo)+1 p-rows; input
@@ -616,13 +608,11 @@ static bool fwd_stem_gemm_impl(at::Tensor x, at::Tensor w, at::Tensor bias,
         slab_p = slab.data_ptr<float>();
       }
       DISPATCH_16(x, T16, {
-        hipLaunchKernelGGL((conv_fwd_stem_strip<T16, R_, STRIDE_>), grid,
-                           dim3(256), smem, cur_stream(),
-                           (const T16*)x.data_ptr(),
-                           (const T16*)w24.data_ptr(),
-                           has_bias ? bias.data_ptr<float>() : nullptr,
-                           slab_p, (T16*)y.data_ptr(), N, H, W, KO, Ho, Wo,
-                           (int)pad, (int)act, has_bias, nrows, sstride);
+        launch256(conv_fwd_stem_strip<T16, R_, STRIDE_>, grid, smem,
+                  (const T16*)x.data_ptr(), (const T16*)w24.data_ptr(),
+                  has_bias ? bias.data_ptr<float>() : nullptr, slab_p,
+                  (T16*)y.data_ptr(), N, H, W, KO, Ho, Wo, pad, act, has_bias,
+                  nrows, sstride);
       });
       if (slab_p)
         stats_slab_reduce(slab, stats, grid.x, 128, KO);
@@ -631,12 +621,11 @@ static bool fwd_stem_gemm_impl(at::Tensor x, at::Tensor w, at::Tensor bias,
   }
   at::Tensor zp = conv_zero_page(x);
   DISPATCH_16(x, T16, {
-    hipLaunchKernelGGL((conv_fwd_stem_gemm<T16, R_, STRIDE_>), grid,
-                       dim3(256), 0, cur_stream(), (const T16*)x.data_ptr(),
-                       (const T16*)w24.data_ptr(),
-                       has_bias ? bias.data_ptr<float>() : nullptr,
-                       (const T16*)zp.data_ptr(), (T16*)y.data_ptr(), N, H,
-                       W, KO, Ho, Wo, (int)pad, (int)act, has_bias);
+    launch256(conv_fwd_stem_gemm<T16, R_, STRIDE_>, grid, 0,
+              (const T16*)x.data_ptr(), (const T16*)w24.data_ptr(),
+              has_bias ? bias.data_ptr<float>() : nullptr,
+              (const T16*)zp.data_ptr(), (T16*)y.data_ptr(), N, H, W, KO, Ho,
+              Wo, pad, act, has_bias);
   });
   return false;
 }
@@ -652,8 +641,6 @@ bool conv_fwd_stem_gemm_launch(at::Tensor x, at::Tensor w, at::Tensor bias,
   return fwd_stem_gemm_impl<3, 1>(x, w, bias, y, pad, act, stats);
 }
 
-void wgrad_reduce_launch(at::Tensor part, at::Tensor dw, long E, long nz);
-
 template <int R_, int STRIDE_>
 static void wgrad_stem_gemm_impl(at::Tensor x, at::Tensor dy, at::Tensor dw,
                                  long pad) {
@@ -662,20 +649,17 @@ static void wgrad_stem_gemm_impl(at::Tensor x, at::Tensor dy, at::Tensor dw,
   TORCH_CHECK(KO % 64 == 0, "stem wgrad GEMM expects KO % 64 == 0");
   const long M = (long)N * Ho * Wo;
   const long E = (long)KO * 3 * R_ * R_;
-  long nchunks = std::min<long>(512, cdiv_l(M, 4096));
-  const long m_per_chunk = cdiv_l(M, std::max<long>(nchunks, 1));
-  nchunks = cdiv_l(M, m_per_chunk);
-  auto part = at::empty({nchunks * E}, x.options().dtype(at::kFloat));
+  const SplitPlan sp = split_plan(M, std::min<long>(512, cdiv_l(M, 4096)));
+  auto part = at::empty({sp.n * E}, x.options().dtype(at::kFloat));
   at::Tensor zp = conv_zero_page(x);
-  dim3 grid(KO / 64, (unsigned)nchunks);
+  dim3 grid(KO / 64, (unsigned)sp.n);
   DISPATCH_16(x, T16, {
-    hipLaunchKernelGGL((conv_wgrad_stem_gemm<T16, R_, STRIDE_>), grid,
-                       dim3(256), 0, cur_stream(), (const T16*)x.data_ptr(),
-                       (const T16*)dy.data_ptr(), (const T16*)zp.data_ptr(),
-                       part.data_ptr<float>(), N, H, W, KO, Ho, Wo, (int)pad,
-                       m_per_chunk);
+    launch256(conv_wgrad_stem_gemm<T16, R_, STRIDE_>, grid, 0,
+              (const T16*)x.data_ptr(), (const T16*)dy.data_ptr(),
+              (const T16*)zp.data_ptr(), part.data_ptr<float>(), N, H, W, KO,
+              Ho, Wo, pad, sp.per);
   });
-  wgrad_reduce_launch(part, dw, E, nchunks);
+  wgrad_reduce_launch(part, dw, E, sp.n);
 }
 
 // dw [KO,3,R,R] fp32

@@ -57,6 +57,13 @@ def _close(gpu_t, cpu_t, rtol=RTOL, atol=ATOL):
     ((2, 30, 30, 3), 64, 7, 2, 3, False, None),    # stem7 GEMM v2 fallback (15x15 out)
     ((2, 29, 29, 3), 32, 7, 2, 3, False, None),    # stem7 odd W, K<64
     ((2, 10, 10, 24), 64, 3, 1, 1, False, None),   # GENC C=24
+    # C=3/6 fallbacks below the stem GEMM (K < 64 or no GEMM shape)
+    ((2, 8, 8, 3), 16, 3, 1, 1, True, "relu"),     # stem3 LDS fwd+wgrad: vector fill (3W%8==0), vector dy stage
+    ((2, 7, 7, 3), 6, 3, 1, 1, False, None),       # stem3 LDS: scalar fill (3W=21), scalar dy stage (Wo*K=42)
+    ((2, 16, 16, 3), 32, 7, 2, 3, False, None),    # stem7 LDS fwd vector fill (3W=48) + stem7 LDS wgrad
+    ((2, 9, 9, 3), 16, 3, 2, 1, False, None),      # smallc<3,3> fwd+wgrad, stride 2
+    ((2, 8, 8, 6), 16, 3, 1, 1, True, None),       # smallc<6,3> fwd
+    ((2, 12, 12, 3), 8, 7, 1, 3, False, None),     # wgrad smallc<3,7>, stride 1
 ])
 def test_conv2d_fwd_bwd(shape, K, ksz, stride, pad, bias, act):
     C = shape[-1]
