@@ -293,6 +293,40 @@ def wgradperf():
     dt = (time.perf_counter() - t0) / 20 * 1e6
     gf = 2 * N * H * W * 64 * 64 * 9 / 1e9
     print(f"wgrad layer1: {dt:.1f} us/call  ({gf / dt * 1e3:.0f} TF)")
+    del x, dy
+    # the four 3x3/s1 shapes of the r18 b8192 benchmark, hip-event timed
+    # (knobs are read once per process: A/B them in separate processes)
+    for hw, c in ((32, 64), (16, 128), (8, 256), (4, 512)):
+        N = 8192
+        x = torch.randn(N, hw, hw, c, device="cuda").to(torch.bfloat16)
+        dy = torch.randn(N, hw, hw, c, device="cuda").to(torch.bfloat16)
+        for _ in range(3):
+            O.ext().conv2d_wgrad(x, dy, 3, 3, 1, 1)
+        evs = [torch.cuda.Event(enable_timing=True) for _ in range(11)]
+        evs[0].record()
+        for i in range(10):
+            O.ext().conv2d_wgrad(x, dy, 3, 3, 1, 1)
+            evs[i + 1].record()
+        torch.cuda.synchronize()
+        ts = sorted(evs[i].elapsed_time(evs[i + 1]) * 1e3 for i in range(10))
+        gf = 2 * N * hw * hw * c * c * 9 / 1e9
+        print(f"wgrad b{N} {hw}x{hw}x{c}: median {ts[5]:.0f} us "
+              f"(min {ts[0]:.0f}, max {ts[-1]:.0f})  "
+              f"{gf / ts[5] * 1e3:.0f} TF/s")
+        del x, dy
+
+
+def pmcwgrad():
+    """A few 3x3 wgrad calls at the r18 b8192 layer-1 shape and nothing
+    else, for a rocprofv3 --pmc pass over whichever kernel the
+    MI355X_WGRAD_T9 knob selects."""
+    import mi355x.ops as O
+    x = torch.randn(8192, 32, 32, 64, device="cuda").to(torch.bfloat16)
+    dy = torch.randn_like(x)
+    for _ in range(6):
+        O.ext().conv2d_wgrad(x, dy, 3, 3, 1, 1)
+    torch.cuda.synchronize()
+    print("pmcwgrad done")
 
 
 def pmcs3():
@@ -348,6 +382,8 @@ if __name__ == "__main__":
         membw()
     if what == "pmcs3":
         pmcs3()
+    if what == "pmcwgrad":
+        pmcwgrad()
     if what == "pmcprobe":
         pmcprobe()
     if what == "r50fwd":

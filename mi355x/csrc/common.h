@@ -31,6 +31,7 @@ struct F16<__half> {
 typedef __attribute__((ext_vector_type(8))) short short8;
 typedef __attribute__((ext_vector_type(4))) short short4v;
 typedef __attribute__((ext_vector_type(4))) float float4v;
+typedef __attribute__((ext_vector_type(4))) int int4v;
 
 constexpr int kWave = 64;  // CDNA4 wavefront width
 

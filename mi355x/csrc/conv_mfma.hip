@@ -1360,6 +1360,169 @@ __global__ __launch_bounds__(256, SCALED ? 3 : 2) void conv_wgrad_mfma_s3(
   }
 }
 
+// nine-tap wgrad for 3x3/stride-1/pad-1 convs whose 64-position m-step is
+// a whole number of output rows inside one image (Wo in {8,16,32},
+// Ho*Wo % 64 == 0): ONE block computes all 9 taps of a 64(k) x 64(c) tile
+// from ONE dy stage and ONE x stage per step, where the s3 kernel spends
+// three blocks that each stage the same dy tile and a row-shifted copy of
+// the same x rows. The x stage is the step's 64/Wo output rows plus one
+// input row above and below, gathered once and written as three s-shifted
+// transposed [c][position] images (position = input row * Wo + q, row 0 =
+// the row above the step). A B fragment of tap (r, s) is image s read at
+// position offset r*Wo: a whole-row offset, so every fragment read stays a
+// 16-byte aligned ds_read_b128. Rows outside the image are staged as
+// zeros; halo rows at a chunk boundary are ordinary rows of the same image
+// and are loaded. The s shift comes from the neighbouring lane group (a
+// wave stages 32 consecutive positions = whole rows), so each x element is
+// requested from memory once per step.
+// Both images use the k-minor staging map and rotate-swizzled columns of
+// the s3 kernel; the x image is 128 columns wide so the rotation wraps
+// with a mask.
+constexpr int T9CL = 128;       // x image columns (>= 64 + 2*Wo, power of 2)
+constexpr int T9LD = T9CL + 8;  // x image row length (+16B, as LDM)
+
+template <typename T16, int WO>
+__global__ __launch_bounds__(256, 2) void conv_wgrad_mfma_t9(
+    const T16* __restrict__ x,   // [N, Hi, WO, CI]
+    const T16* __restrict__ dy,  // [M, KO]
+    float* __restrict__ dw,      // chunk slabs of [KO, 3*3*CI]
+    const int Hi, const int CI, const int KO, const long Mtot,
+    const long m_per_chunk) {
+  static_assert(WGM % WO == 0 && WO % 8 == 0 && 32 % WO == 0 &&
+                WGM + 2 * WO <= T9CL);
+  constexpr int NPOS = WGM + 2 * WO;  // staged input positions per step
+  __shared__ T16 lds[64 * LDM + 3 * 64 * T9LD];
+  T16* const ldsX = lds + 64 * LDM;
+
+  const int tid = threadIdx.x;
+  const int k0 = blockIdx.x * 64;
+  const int c0 = blockIdx.y * 64;
+  const long m_begin = (long)blockIdx.z * m_per_chunk;
+  const long m_end = min(Mtot, m_begin + m_per_chunk);
+
+  // staging: the upper 128 threads stage dy (4 m x 8 k each); thread t
+  // stages x positions 4*(t/8)..+3 x 8 channels while they are < NPOS
+  const bool do_dy = tid >= 128;
+  const int sm = ((tid & 127) >> 3) * 4;
+  const int sk = (tid & 7) * 8;
+  const int xpos = (tid >> 3) * 4;
+  const bool do_x = xpos < NPOS;
+  const int xi = xpos / WO;  // input row of the stage, 0 = row above
+  const int xq = xpos % WO;
+
+  const int wave = tid >> 6;
+  const int lane = tid & 63;
+  const int li = lane & 31;
+  const int kh = lane >> 5;
+  const int i0 = (wave & 1) * 32;   // KO sub-tile
+  const int j0 = (wave >> 1) * 32;  // CI sub-tile
+
+  f32x16 acc[9] = {};
+
+  // first output row of the step (steps never span images)
+  int p0 = (int)((m_begin / WO) % Hi);
+
+  short8 vdy[4], vx[4] = {};
+  short xkeep = 0;  // 0 when this thread's input row lies outside the image
+  auto load_m = [&](long m0) {
+    if (do_dy) {
+#pragma unroll
+      for (int mi = 0; mi < 4; ++mi)
+        vdy[mi] = *reinterpret_cast<const short8*>(
+            dy + (m0 + sm + mi) * KO + k0 + sk);
+    }
+    if (do_x) {
+      // Hi == Ho and Wi == Wo: pixel (n, p0, 0) has linear index m0, and
+      // the stage's rows are contiguous from one row before it
+      const bool ok = (unsigned)(p0 - 1 + xi) < (unsigned)Hi;
+      xkeep = ok ? (short)-1 : (short)0;
+      const T16* xp = x + (ok ? (m0 - WO + xpos) * CI : 0) + c0 + sk;
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        vx[j] = *reinterpret_cast<const short8*>(xp + (long)j * CI);
+    }
+    p0 += WGM / WO;
+    if (p0 >= Hi) p0 = 0;
+  };
+  auto stage_m = [&]() {
+    if (do_dy) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        short4v pk = {vdy[0][e], vdy[1][e], vdy[2][e], vdy[3][e]};
+        const int col = (sm + sk) & 63;  // (sk + e) & 56 == sk
+        *reinterpret_cast<short4v*>(
+            reinterpret_cast<short*>(lds + (sk + e) * LDM + col)) = pk;
+      }
+    }
+    // every lane runs the exchange (idle lanes carry unused values)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) vx[j] &= xkeep;
+    // q-1 of the first and q+1 of the last position: lane group -1 / +1 of
+    // the same wave; zero at the row ends (the pad column)
+    int4v hl = __builtin_bit_cast(int4v, vx[3]);
+    int4v hr = __builtin_bit_cast(int4v, vx[0]);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      hl[u] = __shfl_up(hl[u], 8, 64);
+      hr[u] = __shfl_down(hr[u], 8, 64);
+    }
+    if (do_x) {
+      const short8 zero{};
+      const short8 vl = xq > 0 ? __builtin_bit_cast(short8, hl) : zero;
+      const short8 vr = xq + 4 < WO ? __builtin_bit_cast(short8, hr) : zero;
+      const int col = (xpos + sk) & (T9CL - 1);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        short* row = reinterpret_cast<short*>(ldsX + (sk + e) * T9LD + col);
+        short4v s0 = {vl[e], vx[0][e], vx[1][e], vx[2][e]};
+        short4v s1 = {vx[0][e], vx[1][e], vx[2][e], vx[3][e]};
+        short4v s2 = {vx[1][e], vx[2][e], vx[3][e], vr[e]};
+        *reinterpret_cast<short4v*>(row) = s0;
+        *reinterpret_cast<short4v*>(row + 64 * T9LD) = s1;
+        *reinterpret_cast<short4v*>(row + 2 * 64 * T9LD) = s2;
+      }
+    }
+  };
+
+  load_m(m_begin);
+  for (long m0 = m_begin; m0 < m_end; m0 += WGM) {
+    __syncthreads();
+    stage_m();
+    __syncthreads();
+    if (m0 + WGM < m_end) load_m(m0 + WGM);
+    const int arow = i0 + li;
+    const int brow = j0 + li;
+    const int acol = kh * 8 + (arow & 56);
+    const int bcol = kh * 8 + (brow & 56);
+    const T16* ap = lds + arow * LDM;
+    const T16* bp = ldsX + brow * T9LD;
+#pragma unroll
+    for (int kk = 0; kk < WGM; kk += 16) {
+      const short8 af =
+          *reinterpret_cast<const short8*>(ap + ((kk + acol) & 63));
+#pragma unroll
+      for (int r = 0; r < 3; ++r) {
+        const int col = (kk + r * WO + bcol) & (T9CL - 1);
+#pragma unroll
+        for (int s = 0; s < 3; ++s) {
+          const short8 bf = *reinterpret_cast<const short8*>(
+              bp + s * 64 * T9LD + col);
+          acc[r * 3 + s] = Mfma32<T16>::run(af, bf, acc[r * 3 + s]);
+        }
+      }
+    }
+  }
+
+  float* slab = dw + (long)blockIdx.z * ((long)KO * CI * 9);
+#pragma unroll
+  for (int reg = 0; reg < 16; ++reg) {
+    const int i = (reg & 3) + 8 * (reg >> 2) + 4 * kh;
+    float* o = slab + ((long)(k0 + i0 + i) * CI + c0 + j0 + li) * 9;
+#pragma unroll
+    for (int rs = 0; rs < 9; ++rs) o[rs] = acc[rs][reg];
+  }
+}
+
 // out[zc][e] = sum over this block-row's z-range of part[z][e] — the
 // z-parallel first level of the two-level reduce (small E can't fill the
 // chip with element-parallelism alone)
@@ -1503,8 +1666,9 @@ struct WgradSplit {
   long E;
   at::Tensor part;
 };
-WgradSplit wgrad_split(long M, long E, const at::Tensor& dw, long cap) {
-  long want = std::min<long>(cdiv_l(M, 4096), 4096);
+WgradSplit wgrad_split(long M, long E, const at::Tensor& dw, long cap,
+                       long depth = 4096) {
+  long want = std::min<long>(cdiv_l(M, depth), 4096);
   if (cap > 0) want = std::min(want, cap);
   const SplitPlan p = split_plan(M, want, WGM);
   return {p.per, (int)p.n, E,
@@ -1532,6 +1696,26 @@ void wgrad_s3_launch(const WgradArgs& a, int KT, WgradMode mode,
         constexpr WgradMode M_ = decltype(m)::value;
         go(conv_wgrad_mfma_s3<T16, 64, M_ == WG_SCALED, M_ == WG_KMIN>);
       });
+  });
+}
+
+// conv_wgrad_mfma_t9: one block per (k-tile, c-tile, chunk), all nine taps
+bool wgrad_t9_eligible(const WgradArgs& a) {
+  return a.R == 3 && a.S == 3 && a.stride == 1 && a.pad == 1 &&
+         a.Hi == a.Ho && a.Wi == a.Wo && !a.asc &&
+         (a.Wo == 8 || a.Wo == 16 || a.Wo == 32) &&
+         (a.Ho * a.Wo) % WGM == 0 && a.KO % 64 == 0 && a.CI % 64 == 0;
+}
+void wgrad_t9_launch(const WgradArgs& a, const WgradSplit& sp) {
+  dim3 grid(a.KO / 64, a.CI / 64, sp.nchunks);
+  const long M = (long)a.N * a.Ho * a.Wo;
+  DISPATCH_16(a.x, T16, {
+    pick<8, 16, 32>(a.Wo, [&](auto wo) {
+      launch256(conv_wgrad_mfma_t9<T16, decltype(wo)::value>, grid, 0,
+                (const T16*)a.x.data_ptr(), (const T16*)a.dy.data_ptr(),
+                sp.part.data_ptr<float>(), a.Hi, a.CI, a.KO, M,
+                sp.m_per_chunk);
+    });
   });
 }
 
@@ -1582,6 +1766,23 @@ void conv_wgrad_mfma_launch(at::Tensor x, at::Tensor dy, at::Tensor dw,
                     (int)dy.size(2), (int)R, (int)S, (int)stride, (int)pad};
   const long M = (long)a.N * a.Ho * a.Wo;
   const long E = (long)a.KO * R * S * a.CI;
+  // nine taps per block where an m-step is whole output rows of one image
+  // (MI355X_WGRAD_T9=0 restores the s3 path)
+  static const bool t9_on = EnvKnob("MI355X_WGRAD_T9").on();
+  if (t9_on && wgrad_t9_eligible(a)) {
+    // Chunk depth stays at the s3 kernel's 4096 m: with the same chunks
+    // every dw element is summed in the same order, so the result is bit
+    // for bit the s3 kernel's. Deeper chunks are faster at large M (fewer
+    // 147 KB partial slabs: b8192 layers 1/2/3 at 4096 / 8192 / 16384 m:
+    // 928/906/882, 760/707/688, 751/694/669 us) but starve the chip at
+    // small M (layer 1 at b256: 117 / 213 / 410 us) and change the order.
+    static const long depth = EnvKnob("MI355X_T9_DEPTH").num(4096);
+    const WgradSplit sp = wgrad_split(M, E, dw, wgrad_chunk_cap(),
+                                      std::max<long>(depth, WGM));
+    wgrad_t9_launch(a, sp);
+    wgrad_split_finish(sp, dw);
+    return;
+  }
   // 3x3/s1/p1: s-grouped kernel (3 taps per stage) — MI355X_WGRAD_S3=0
   // falls back to the tap-per-block kernel
   static const bool s3_on = EnvKnob("MI355X_WGRAD_S3").on();
