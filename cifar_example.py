@@ -14,6 +14,10 @@ Env overrides (benchmark configs; CLI shape unchanged):
   MI355X_DEVICE=cpu|cuda                    (default cpu, like the reference)
   MI355X_CKPT=path                          checkpoint path (default the
                                             reference's ./cifar_net.pth)
+  MI355X_DEVICE_DATA=1                      device-resident dataset
+                                            (DeviceLoader) for train and test
+  MI355X_AUGMENT=1                          pad-4 random crop + flip on the
+                                            train loader (needs DEVICE_DATA)
 """
 
 import os
@@ -22,7 +26,8 @@ import time
 import torch
 
 from mi355x import optim
-from mi355x.data import CIFAR10, DataLoader, SyntheticImageDataset
+from mi355x.data import (CIFAR10, Augment, DataLoader, DeviceLoader,
+                         SyntheticImageDataset)
 from mi355x.models import build_model
 from mi355x.ops import cross_entropy
 from mi355x.parallel.flat import FlatState
@@ -49,12 +54,24 @@ def main():
     trainset, testset = get_datasets()
     # num_workers=2 mirrors the reference surface (cifar_example.py:47,52);
     # our loader needs no worker processes (see mi355x/data.py)
-    trainloader = DataLoader(trainset, batch_size=batch, shuffle=True,
-                             num_workers=2,
-                             device=device if device.type == "cuda" else None)
-    testloader = DataLoader(testset, batch_size=batch, shuffle=False,
-                            num_workers=2,
-                            device=device if device.type == "cuda" else None)
+    if os.environ.get("MI355X_DEVICE_DATA", "0") == "1":
+        # dataset resident on the device as uint8; one fused kernel per
+        # batch builds it (gather + crop/flip + normalize + NHWC 16-bit)
+        augment = (Augment(pad=4, flip=True)
+                   if os.environ.get("MI355X_AUGMENT", "0") == "1" else None)
+        trainloader = DeviceLoader(trainset, batch_size=batch, shuffle=True,
+                                   device=device, augment=augment)
+        testloader = DeviceLoader(testset, batch_size=batch, shuffle=False,
+                                  device=device)
+    else:
+        if os.environ.get("MI355X_AUGMENT", "0") == "1":
+            raise SystemExit("MI355X_AUGMENT=1 needs MI355X_DEVICE_DATA=1")
+        trainloader = DataLoader(trainset, batch_size=batch, shuffle=True,
+                                 num_workers=2,
+                                 device=device if device.type == "cuda" else None)
+        testloader = DataLoader(testset, batch_size=batch, shuffle=False,
+                                num_workers=2,
+                                device=device if device.type == "cuda" else None)
 
     net = build_model(os.environ.get("MI355X_MODEL", "net")).to(device)
     flat = FlatState(net)

@@ -19,7 +19,10 @@ Launch:  python -m mi355x.launcher --nproc-per-node 8 cifar_example_ddp.py
 Env overrides (benchmark configs; CLI shape unchanged): MI355X_MODEL,
 MI355X_SYNTHETIC, MI355X_BATCH, MI355X_EPOCHS, MI355X_STEPS, MI355X_LR,
 MI355X_SYNC_BN=1, MI355X_FP16=1 (fp16 compute + dynamic loss scaling),
-MI355X_CKPT (checkpoint path, default ./cifar_net.pth).
+MI355X_CKPT (checkpoint path, default ./cifar_net.pth),
+MI355X_DEVICE_DATA=1 (device-resident dataset for train and test),
+MI355X_AUGMENT=1 (pad-4 random crop + flip on the train loader; needs
+MI355X_DEVICE_DATA).
 """
 
 import argparse
@@ -29,7 +32,8 @@ import time
 import torch
 
 from mi355x import optim
-from mi355x.data import CIFAR10, DataLoader, DistributedSampler, SyntheticImageDataset
+from mi355x.data import (CIFAR10, Augment, DataLoader, DeviceLoader,
+                         DistributedSampler, SyntheticImageDataset)
 from mi355x.metrics import DistAccuracy
 from mi355x.models import build_model
 from mi355x.ops import cross_entropy
@@ -77,10 +81,24 @@ def main(args):
     sampler_test = DistributedSampler(testset, num_replicas=args.world_size,
                                       rank=args.rank, shuffle=False)
     dev_for_loader = device if use_cuda else None
-    trainloader = DataLoader(trainset, batch_size=batch, sampler=sampler_train,
-                             device=dev_for_loader)
-    testloader = DataLoader(testset, batch_size=batch, sampler=sampler_test,
-                            device=dev_for_loader)
+    if os.environ.get("MI355X_DEVICE_DATA", "0") == "1":
+        # dataset resident on the device as uint8; one fused kernel per
+        # batch. The draws key on the dataset index and the sampler's
+        # epoch, so a sample augments the same on every rank.
+        augment = (Augment(pad=4, flip=True)
+                   if os.environ.get("MI355X_AUGMENT", "0") == "1" else None)
+        trainloader = DeviceLoader(trainset, batch_size=batch,
+                                   sampler=sampler_train,
+                                   device=dev_for_loader, augment=augment)
+        testloader = DeviceLoader(testset, batch_size=batch,
+                                  sampler=sampler_test, device=dev_for_loader)
+    else:
+        if os.environ.get("MI355X_AUGMENT", "0") == "1":
+            raise SystemExit("MI355X_AUGMENT=1 needs MI355X_DEVICE_DATA=1")
+        trainloader = DataLoader(trainset, batch_size=batch,
+                                 sampler=sampler_train, device=dev_for_loader)
+        testloader = DataLoader(testset, batch_size=batch,
+                                sampler=sampler_test, device=dev_for_loader)
 
     net = build_model(os.environ.get("MI355X_MODEL", "net")).to(device)
     if os.environ.get("MI355X_SYNC_BN", "0") == "1":

@@ -1,6 +1,7 @@
 // pybind bindings for the mi355x gfx950 kernel library.
 #include <torch/extension.h>
 
+#include <tuple>
 #include <vector>
 
 at::Tensor relu_bwd(at::Tensor dy, at::Tensor y);
@@ -63,6 +64,11 @@ std::vector<at::Tensor> cross_entropy_fwd(at::Tensor logits,
 at::Tensor cross_entropy_bwd(at::Tensor logits, at::Tensor target,
                              at::Tensor lse, at::Tensor dloss);
 
+std::tuple<at::Tensor, at::Tensor> gather_augment(
+    at::Tensor data_u8, at::Tensor targets, at::Tensor indices,
+    at::Tensor scale, at::Tensor shift, int64_t pad, bool flip, int64_t seed,
+    int64_t epoch, at::Tensor like);
+
 void register_rccl(py::module_& m);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -94,4 +100,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_nt_mfma", &gemm_nt_mfma);
   m.def("cross_entropy_fwd", &cross_entropy_fwd);
   m.def("cross_entropy_bwd", &cross_entropy_bwd);
+  m.def("gather_augment", &gather_augment);
 }

@@ -23,6 +23,10 @@ these are mandatory, not convenience):
                          for worker processes + pin_memory: CIFAR batches are
                          tiny, so prefetch depth 1 on a copy stream hides the
                          whole transfer behind compute).
+  DeviceLoader           the dataset lives in HBM as uint8 NHWC; each batch
+                         is one fused HIP kernel (gather by sampler index,
+                         pad-4 random crop + flip per Augment, normalize,
+                         16-bit NHWC out) — no host work or H2D per step.
 """
 
 from __future__ import annotations
@@ -41,6 +45,9 @@ __all__ = [
     "SyntheticImageDataset",
     "DistributedSampler",
     "DataLoader",
+    "augment_params",
+    "Augment",
+    "DeviceLoader",
 ]
 
 
@@ -144,6 +151,9 @@ class CIFAR10:
         raw = np.concatenate(datas, axis=0).reshape(-1, 3, 32, 32)
         # (x/255 - 0.5)/0.5 == x * (2/255) - 1 : one fused pass, float32 CHW
         self.data = torch.from_numpy(raw.astype(np.float32) * (2.0 / 255.0) - 1.0)
+        # the raw bytes as NHWC, for DeviceLoader (device-resident dataset)
+        self.data_u8 = torch.from_numpy(
+            np.ascontiguousarray(raw.transpose(0, 2, 3, 1)))
         self.targets = torch.tensor(labels, dtype=torch.int64)
         self.classes = list(CIFAR10_CLASSES)
 
@@ -168,6 +178,17 @@ class SyntheticImageDataset:
         self.targets = torch.randint(0, num_classes, (n,), generator=g,
                                      dtype=torch.int64)
         self.classes = [str(i) for i in range(num_classes)]
+        self._data_u8 = None
+
+    @property
+    def data_u8(self) -> torch.Tensor:
+        """(N,H,W,C) uint8 view of ``.data`` for DeviceLoader, derived on
+        first use as round((data+1)*127.5) — no generator call, so ``.data``
+        and ``.targets`` are exactly what they were without it."""
+        if self._data_u8 is None:
+            q = torch.round((self.data + 1) * 127.5).clamp_(0, 255)
+            self._data_u8 = q.to(torch.uint8).permute(0, 2, 3, 1).contiguous()
+        return self._data_u8
 
     def __len__(self) -> int:
         return self.data.shape[0]
@@ -373,3 +394,160 @@ class DataLoader:
             pending = nxt
         if pending is not None:
             yield handover(pending)
+
+
+# ---------------------------------------------------------------------------
+# Device-resident dataset: one fused gather/crop/flip/normalize kernel/batch
+# ---------------------------------------------------------------------------
+
+_M32 = np.uint64(0xFFFFFFFF)
+_GOLDEN = 0x9E3779B9
+
+
+def _mix32(h: np.ndarray) -> np.ndarray:
+    """uint32 avalanche hash on uint64 carriers (products masked to 32 bits;
+    uint64 multiplication wraps, so the low 32 bits are exact)."""
+    h = h ^ (h >> np.uint64(16))
+    h = (h * np.uint64(0x7FEB352D)) & _M32
+    h = h ^ (h >> np.uint64(15))
+    h = (h * np.uint64(0x846CA68B)) & _M32
+    h = h ^ (h >> np.uint64(16))
+    return h
+
+
+def augment_params(seed: int, epoch: int, indices, pad: int, flip: bool):
+    """Crop offsets and flip bits of the samples ``indices`` in ``epoch``:
+    ``(dy, dx, f)`` int64 tensors, dy/dx in [0, 2*pad], f in {0, 1}.
+
+    Counter-based and keyed on the dataset index, so a sample's augmentation
+    in an epoch is the same at any batch size, world size or rank. This is
+    the CPU twin of the device function in csrc/augment.hip (uint32
+    arithmetic throughout) and the oracle of its tests.
+    """
+    if not 0 <= pad <= 32767:  # dy/dx are 16.16 fixed-point uint32 products
+        raise ValueError(f"pad must be in [0, 32767], got {pad}")
+    i = np.asarray(torch.as_tensor(indices, dtype=torch.int64).numpy())
+    if i.size and (i.min() < 0 or i.max() > 0xFFFFFFFF):
+        raise ValueError("augment_params: index outside uint32 range")
+    i = i.astype(np.uint64)
+    key0 = ((int(seed) & 0xFFFFFFFF) * _GOLDEN + (int(epoch) & 0xFFFFFFFF)) \
+        & 0xFFFFFFFF
+    key = _mix32(np.array(key0, dtype=np.uint64))
+    h = _mix32(i ^ key)
+    h2 = _mix32((h + np.uint64(_GOLDEN)) & _M32)
+    span = np.uint64(2 * pad + 1)
+    dy = (((h & np.uint64(0xFFFF)) * span) & _M32) >> np.uint64(16)
+    dx = (((h >> np.uint64(16)) * span) & _M32) >> np.uint64(16)
+    f = (h2 & np.uint64(1)) if flip else np.zeros_like(h2)
+    return tuple(torch.from_numpy(a.astype(np.int64)) for a in (dy, dx, f))
+
+
+class Augment:
+    """Train-time augmentation settings: zero-pad by ``pad`` and take a
+    random crop of the original size, then flip horizontally with
+    probability 1/2 (the torchvision RandomCrop(padding=pad) +
+    RandomHorizontalFlip recipe). ``augment=None`` on a loader means none."""
+
+    def __init__(self, pad: int = 4, flip: bool = True):
+        self.pad = int(pad)
+        self.flip = bool(flip)
+
+    def __repr__(self) -> str:
+        return f"Augment(pad={self.pad}, flip={self.flip})"
+
+
+class DeviceLoader:
+    """Loader over a dataset that lives on the device as uint8 NHWC.
+
+    Construction uploads ``dataset.data_u8`` / ``.targets`` once (CIFAR-10
+    train is 150 MB). Each ``__iter__`` uploads the epoch's indices once as
+    int32; every batch is then one ``ops.gather_augment`` call on the current
+    stream over a slice of them: gather, pad+crop, flip, normalize with
+    ``mean``/``std``, convert to the compute dtype, write NHWC. No host
+    sync, H2D copy or pinned staging per batch.
+
+    Same index plan as :class:`DataLoader` (sampler wins over ``shuffle``;
+    ``randperm`` seeded ``seed + epoch``; ``drop_last``; ``__len__``). The
+    augmentation epoch is the sampler's ``epoch`` when it has one (so
+    ``set_epoch`` drives shuffle and augmentation together), else the
+    loader's own counter.
+
+    Yields ``(x, y)`` with x the NHWC buffer viewed as logical NCHW, so the
+    models' ``to_model_layout`` permute back is contiguous already and
+    copies nothing. ``device=None`` or a CPU device runs the CPU op (fp32).
+    """
+
+    def __init__(self, dataset, batch_size: int = 1, shuffle: bool = False,
+                 sampler: Optional[Sequence[int]] = None,
+                 drop_last: bool = False, device=None,
+                 augment: Optional[Augment] = None,
+                 mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5), seed: int = 0):
+        self.dataset = dataset
+        self.batch_size = batch_size
+        self.shuffle = shuffle
+        self.sampler = sampler
+        self.drop_last = drop_last
+        self.device = torch.device(device) if device is not None \
+            else torch.device("cpu")
+        self.augment = augment
+        self.seed = seed
+        self._epoch = 0
+        data_u8 = dataset.data_u8
+        C = data_u8.shape[3]
+        mean64 = np.asarray(mean, dtype=np.float64).reshape(-1)
+        std64 = np.asarray(std, dtype=np.float64).reshape(-1)
+        if mean64.size != C or std64.size != C:
+            raise ValueError(
+                f"mean/std need one value per channel ({C}), got "
+                f"{mean64.size}/{std64.size}")
+        # (u8/255 - mean)/std == u8 * scale + shift
+        self.scale = torch.from_numpy(
+            (1.0 / (255.0 * std64)).astype(np.float32)).to(self.device)
+        self.shift = torch.from_numpy(
+            (-mean64 / std64).astype(np.float32)).to(self.device)
+        self.data_u8 = data_u8.contiguous().to(self.device)
+        self.targets = dataset.targets.to(torch.int64).to(self.device)
+
+    def __len__(self) -> int:
+        n = len(self.sampler) if self.sampler is not None \
+            else len(self.dataset)
+        if self.drop_last:
+            return n // self.batch_size
+        return math.ceil(n / self.batch_size)
+
+    def _indices(self):
+        if self.sampler is not None:
+            return list(iter(self.sampler))
+        n = len(self.dataset)
+        if self.shuffle:
+            g = torch.Generator()
+            g.manual_seed(self.seed + self._epoch)
+            return torch.randperm(n, generator=g).tolist()
+        return list(range(n))
+
+    def __iter__(self):
+        from mi355x import ops
+
+        idx = torch.as_tensor(self._indices(), dtype=torch.int64)
+        aug_epoch = int(getattr(self.sampler, "epoch", self._epoch))
+        self._epoch += 1
+        n = self.data_u8.shape[0]
+        # host-side bounds check, before anything is launched
+        if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= n):
+            bad = idx[(idx < 0) | (idx >= n)][0].item()
+            raise IndexError(
+                f"DeviceLoader: sampler index {bad} outside dataset of {n}")
+        idx_dev = idx.to(torch.int32).to(self.device)
+        pad = self.augment.pad if self.augment is not None else 0
+        flip = self.augment.flip if self.augment is not None else False
+        bs = self.batch_size
+        total = idx.numel()
+        for s in range(0, total, bs):
+            e = min(s + bs, total)
+            if self.drop_last and e - s < bs:
+                break
+            x, y = ops.gather_augment(
+                self.data_u8, self.targets, idx_dev[s:e], self.scale,
+                self.shift, pad=pad, flip=flip, seed=self.seed,
+                epoch=aug_epoch)
+            yield x.permute(0, 3, 1, 2), y

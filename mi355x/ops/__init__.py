@@ -4,6 +4,7 @@ from .functional import (  # noqa: F401
     compute_dtype,
     conv2d,
     cross_entropy,
+    gather_augment,
     global_avg_pool,
     linear,
     max_pool2d,

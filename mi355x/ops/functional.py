@@ -603,6 +603,52 @@ def cross_entropy(logits, target):
 
 
 # ---------------------------------------------------------------------------
+# batch building from a device-resident uint8 dataset
+# ---------------------------------------------------------------------------
+
+
+def gather_augment(data_u8, targets, indices, scale, shift, *, pad=0,
+                   flip=False, seed=0, epoch=0):
+    """Build a batch from the uint8 NHWC dataset: gather ``indices``,
+    zero-pad by ``pad`` and crop at a random offset, flip, then
+    ``v*scale[c] + shift[c]`` (a padded pixel is raw 0, so it comes out as
+    shift[c] — the torchvision crop -> flip -> normalize order). The draws
+    are ``mi355x.data.augment_params(seed, epoch, indices, pad, flip)``.
+
+    Returns (x NHWC, y int64). GPU: one kernel, x in the compute dtype,
+    indices int32. CPU: fp32. pad=0, flip=False is the eval path (gather +
+    normalize + layout only). No autograd.
+
+    ``indices`` must lie in [0, N). The CPU path raises IndexError
+    otherwise; the kernel cannot raise, so it reads nothing for such an
+    index and returns an all-padding image with label -1 (which the
+    cross-entropy kernel turns into a NaN loss). DeviceLoader checks the
+    epoch's indices on the host before it launches anything.
+    """
+    if data_u8.is_cuda:
+        like = torch.empty(0, dtype=compute_dtype(), device=data_u8.device)
+        x, y = ext().gather_augment(data_u8, targets, indices, scale, shift,
+                                    int(pad), bool(flip), int(seed),
+                                    int(epoch), like)
+        return x, y
+    from mi355x.data import augment_params
+
+    N, H, W, _ = data_u8.shape
+    idx = indices.to(torch.int64)
+    if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= N):
+        raise IndexError(f"gather_augment: index outside dataset of {N}")
+    dy, dx, f = augment_params(seed, epoch, idx, pad, flip)
+    sh = torch.arange(H)[None, :] + (dy[:, None] - pad)             # (B,H)
+    ww = torch.arange(W)[None, :]
+    sw = torch.where(f[:, None] != 0, W - 1 - ww, ww) + (dx[:, None] - pad)
+    ok = ((sh >= 0) & (sh < H))[:, :, None] & ((sw >= 0) & (sw < W))[:, None, :]
+    v = data_u8[idx[:, None, None], sh.clamp(0, H - 1)[:, :, None],
+                sw.clamp(0, W - 1)[:, None, :]]                     # (B,H,W,C)
+    v = v.to(torch.float32) * ok[..., None]
+    return v * scale + shift, targets[idx]
+
+
+# ---------------------------------------------------------------------------
 # fused optimizer step
 # ---------------------------------------------------------------------------
 
