@@ -135,30 +135,52 @@ def r50_fwd_steps():
 
 
 def convperf():
-    """fwd conv timing per layer shape (patch vs per-tap gather A/B via
-    MI355X_CONV_PATCH)."""
+    """fwd, dgrad and dgrad+ADDIN conv timing per layer shape at the
+    benchmark's batch (r18-CIFAR b8192): the four 3x3/s1 layers (patch
+    kernel) plus one 1x1/s2 and one 3x3/s2 downsample shape (gather fwd,
+    parity dgrad). MI355X_CONV_PATCH=0 gives the per-tap gather A/B."""
     import time
     import mi355x.ops as O
-    shapes = [  # (N,H,W,C,K,ksz,stride,pad) — r18-CIFAR b1024 layers
-        (1024, 32, 32, 64, 64, 3, 1, 1),
-        (1024, 16, 16, 128, 128, 3, 1, 1),
-        (1024, 8, 8, 256, 256, 3, 1, 1),
-        (1024, 4, 4, 512, 512, 3, 1, 1),
+    N = int(os.environ.get("CONVPERF_BATCH", "8192"))
+    shapes = [  # (H,W,C,K,ksz,stride,pad)
+        (32, 32, 64, 64, 3, 1, 1),
+        (16, 16, 128, 128, 3, 1, 1),
+        (8, 8, 256, 256, 3, 1, 1),
+        (4, 4, 512, 512, 3, 1, 1),
+        (32, 32, 64, 128, 1, 2, 0),
+        (32, 32, 64, 128, 3, 2, 1),
     ]
-    e = torch.empty(0, device="cuda")
-    for (N, H, W, C, K, ksz, st, pad) in shapes:
-        x = torch.randn(N, H, W, C, device="cuda").to(torch.bfloat16)
-        w = (torch.randn(K, ksz, ksz, C, device="cuda") * 0.1).to(torch.bfloat16)
+    e32 = torch.empty(0, device="cuda")
+    e16 = torch.empty(0, device="cuda", dtype=torch.bfloat16)
+
+    def timed(fn_):
         for _ in range(3):
-            O.ext().conv2d_fwd(x, w, e, st, pad, 0, ksz, ksz)
+            fn_()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        for _ in range(30):
-            O.ext().conv2d_fwd(x, w, e, st, pad, 0, ksz, ksz)
+        for _ in range(20):
+            fn_()
         torch.cuda.synchronize()
-        us = (time.perf_counter() - t0) / 30 * 1e6
-        tf = 2.0 * N * H * W * K * ksz * ksz * C / st / st / 1e12 / (us / 1e6)
-        print(f"fwd C={C} K={K} {H}x{W}: {us:.1f} us  ({tf:.0f} TF)")
+        return (time.perf_counter() - t0) / 20 * 1e6
+
+    for (H, W, C, K, ksz, st, pad) in shapes:
+        P = (H + 2 * pad - ksz) // st + 1
+        Q = (W + 2 * pad - ksz) // st + 1
+        x = torch.randn(N, H, W, C, device="cuda").to(torch.bfloat16)
+        w = (torch.randn(K, ksz, ksz, C, device="cuda") * 0.1).to(torch.bfloat16)
+        wflip = w.permute(1, 2, 3, 0).contiguous()  # [R,S,C,K]
+        dy = torch.randn(N, P, Q, K, device="cuda").to(torch.bfloat16)
+        flop = 2.0 * N * P * Q * K * ksz * ksz * C
+        for tag, fn_ in [
+            ("fwd", lambda: O.ext().conv2d_fwd(x, w, e32, st, pad, 0, ksz, ksz)),
+            ("dgrad", lambda: O.ext().conv2d_dgrad(dy, wflip, st, pad, H, W,
+                                                   e16)),
+            ("dgrad+addin", lambda: O.ext().conv2d_dgrad(dy, wflip, st, pad,
+                                                         H, W, x)),
+        ]:
+            us = timed(fn_)
+            print(f"{tag:12s} C={C} K={K} {H}x{W} k{ksz}s{st}: {us:8.1f} us  "
+                  f"({flop / 1e12 / (us / 1e6):.0f} TF)", flush=True)
 
 
 def membw():

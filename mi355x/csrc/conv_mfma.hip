@@ -12,6 +12,19 @@
 // tile, 4 waves x (32M x 64N) each as 2 x mfma_f32_32x32x16, LDS tiles
 // [row][BK+8] padded against bank conflicts (G4), T14-style staging
 // (write after barrier, next global load issued under the MFMA phase).
+//
+// Epilogue (conv_epilogue.h): the accumulator has the output channel on
+// the lane and the row in the register, which stored directly is 2 bytes
+// per lane. conv_gather_gemm, conv_dgrad_s2_gemm and the ADDIN variant of
+// conv_patch_gemm instead stage the rounded tile in the A/B (or patch) LDS
+// the main loop is done with and write whole output rows, 16 bytes per
+// lane; a residual ADDIN tile is read the same way. For that their B rows
+// are staged in the order epi_brow gives, so that a lane's NT values are
+// adjacent channels. The plain conv_patch_gemm variants keep the direct
+// store: their stores already hide behind the next blocks' patch fill, and
+// the extra barrier and LDS round trip measured 2% slower
+// (profiles/r04_conv_epilogue.md).
+#include "conv_epilogue.h"
 #include "conv_internal.h"
 
 typedef __attribute__((ext_vector_type(8))) _Float16 half8;
@@ -259,7 +272,8 @@ __global__ __launch_bounds__(256, 2) void conv_gather_gemm(
 #pragma unroll
     for (int i = 0; i < 4; ++i)
       *reinterpret_cast<short8*>(pa + 8 * i) = sa[i];
-    short* pb = reinterpret_cast<short*>(ldsB + sb_n * LDK + sb_c);
+    short* pb =
+        reinterpret_cast<short*>(ldsB + epi_brow<NT>(sb_n) * LDK + sb_c);
 #pragma unroll
     for (int i = 0; i < EPT / 8; ++i)
       *reinterpret_cast<short8*>(pb + 8 * i) = sb[i];
@@ -286,31 +300,50 @@ __global__ __launch_bounds__(256, 2) void conv_gather_gemm(
     }
   }
 
-  // ---- epilogue: bias + act + store (+ optional BN-stats partials) ----
+  // ---- epilogue: bias + act (+ optional BN-stats partials) in fp32
+  // registers, one rounding, then whole-row 16-byte stores through the
+  // wave's LDS region (conv_epilogue.h; lane li holds channels li*NT+t) ----
+  using E = EpiTile<NT>;
+  static_assert(sizeof(lds) >= E::BYTES, "epilogue tile must fit the A/B LDS");
+  short* wl = reinterpret_cast<short*>(lds) + wave * E::WAVE;
+  long roff[E::NIT];
+#pragma unroll
+  for (int it = 0; it < E::NIT; ++it) {
+    const long m = bm0 + wm + epi_io_row<NT>(it, lane);
+    roff[it] = m < Mtot ? m * KO + k0 : -1;
+  }
+  __syncthreads();  // every wave's last MFMA phase is done reading LDS
+  if constexpr (ADDIN) {
+    epi_fetch<T16, NT>(wl, addin, lane, roff);
+    epi_wave_sync();
+  }
   float bv[NT];
   float ssum[NT] = {}, ssq[NT] = {};
 #pragma unroll
   for (int tnt = 0; tnt < NT; ++tnt)
-    bv[tnt] = has_bias ? bias[k0 + tnt * 32 + li] : 0.f;
+    bv[tnt] = has_bias ? bias[k0 + li * NT + tnt] : 0.f;
 #pragma unroll
   for (int reg = 0; reg < 16; ++reg) {
-    const int row = (reg & 3) + 8 * (reg >> 2) + 4 * kh;
-    const long m_out = bm0 + wm + row;
-    if (m_out < Mtot) {
+    const int row = epi_acc_row(reg, kh);
+    typename EpiPack<NT>::type h = {};
+    if (bm0 + wm + row < Mtot) {
+      if constexpr (ADDIN) h = epi_get<NT>(wl, row, li);
 #pragma unroll
       for (int tnt = 0; tnt < NT; ++tnt) {
         float v = acc[tnt][reg] + bv[tnt];
-        if constexpr (ADDIN)
-          v += F16<T16>::to_f32(addin[m_out * KO + k0 + tnt * 32 + li]);
+        if constexpr (ADDIN) v += s16_to_f32<T16>(h[tnt]);
         if (act == 1) v = fmaxf(v, 0.f);
         if (stats_slab) {
           ssum[tnt] += v;
           ssq[tnt] += v * v;
         }
-        out[m_out * KO + k0 + tnt * 32 + li] = F16<T16>::from_f32(v);
+        h[tnt] = f32_to_s16<T16>(v);
       }
     }
+    epi_put<NT>(wl, row, li, h);
   }
+  epi_wave_sync();
+  epi_flush<T16, NT>(wl, out, lane, roff);
   if (stats_slab) {
     // conv->BN fusion: fold the block's per-lane channel partials (8
     // lanes per channel: 4 waves x 2 kh halves) — kh halves via one
@@ -324,12 +357,12 @@ __global__ __launch_bounds__(256, 2) void conv_gather_gemm(
       ssq[tnt] += __shfl_xor(ssq[tnt], 32, 64);
     }
     float* lsum = reinterpret_cast<float*>(lds);  // [4 waves][2*BNTC]
-    __syncthreads();
+    __syncthreads();  // the staged tiles (same LDS) have been read back
     if (kh == 0) {
 #pragma unroll
       for (int tnt = 0; tnt < NT; ++tnt) {
-        lsum[wave * 2 * BNTC + tnt * 32 + li] = ssum[tnt];
-        lsum[wave * 2 * BNTC + BNTC + tnt * 32 + li] = ssq[tnt];
+        lsum[wave * 2 * BNTC + li * NT + tnt] = ssum[tnt];
+        lsum[wave * 2 * BNTC + BNTC + li * NT + tnt] = ssq[tnt];
       }
     }
     __syncthreads();
@@ -480,7 +513,8 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad_s2_gemm(
 #pragma unroll
     for (int i = 0; i < 4; ++i)
       *reinterpret_cast<short8*>(pa_ + 8 * i) = sa[i];
-    short* pb_ = reinterpret_cast<short*>(ldsB + sb_n * LDK + sb_c);
+    short* pb_ =
+        reinterpret_cast<short*>(ldsB + epi_brow<NT>(sb_n) * LDK + sb_c);
 #pragma unroll
     for (int i = 0; i < EPT / 8; ++i)
       *reinterpret_cast<short8*>(pb_ + 8 * i) = sb[i];
@@ -509,9 +543,14 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad_s2_gemm(
     }
   }
 
-  // epilogue: scatter into the strided class positions of dx. One
-  // image-decode per lane; per register only a rem-walk + one div by Wa
-  // (the per-reg /(Ha*Wa) pair was the other half of the issue stalls)
+  // epilogue: scatter into the strided class positions of dx. A row's
+  // channels are contiguous, so rows leave as 16-byte pieces through the
+  // wave's LDS region (conv_epilogue.h). One image-decode per lane; per
+  // moved row only a rem-walk + one div by Wa (per-row /(Ha*Wa) pairs
+  // were half of this kernel's issue stalls)
+  using E = EpiTile<NT>;
+  static_assert(sizeof(lds) >= E::BYTES, "epilogue tile must fit the A/B LDS");
+  short* wl = reinterpret_cast<short*>(lds) + wave * E::WAVE;
   const long m_base = bm0 + wm;
   const int HaWa = Ha * Wa;
   int nn0 = 0, rem0 = 0;
@@ -519,11 +558,12 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad_s2_gemm(
     nn0 = (int)(m_base / HaWa);
     rem0 = (int)(m_base % HaWa);
   }
+  long roff[E::NIT];
 #pragma unroll
-  for (int reg = 0; reg < 16; ++reg) {
-    const int row = (reg & 3) + 8 * (reg >> 2) + 4 * kh;
-    const long m_out = m_base + row;
-    if (m_out < Mc) {
+  for (int it = 0; it < E::NIT; ++it) {
+    const int row = epi_io_row<NT>(it, lane);
+    roff[it] = -1;
+    if (m_base + row < Mc) {
       int nn = nn0, rem = rem0 + row;
       while (rem >= HaWa) {
         rem -= HaWa;
@@ -531,16 +571,29 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad_s2_gemm(
       }
       const int ih = 2 * (rem / Wa) + pa;
       const int iw = 2 * (rem - (rem / Wa) * Wa) + pb;
-      const long off = (((long)nn * H + ih) * W + iw) * CI;
-#pragma unroll
-      for (int tnt = 0; tnt < NT; ++tnt) {
-        float v = acc[tnt][reg];
-        if constexpr (ADDIN)
-          v += F16<T16>::to_f32(addin[off + k0 + tnt * 32 + li]);
-        dx[off + k0 + tnt * 32 + li] = F16<T16>::from_f32(v);
-      }
+      roff[it] = (((long)nn * H + ih) * W + iw) * CI + k0;
     }
   }
+  __syncthreads();  // every wave's last MFMA phase is done reading LDS
+  if constexpr (ADDIN) {
+    epi_fetch<T16, NT>(wl, addin, lane, roff);
+    epi_wave_sync();
+  }
+#pragma unroll
+  for (int reg = 0; reg < 16; ++reg) {
+    const int row = epi_acc_row(reg, kh);
+    typename EpiPack<NT>::type h = {};
+    if constexpr (ADDIN) h = epi_get<NT>(wl, row, li);
+#pragma unroll
+    for (int tnt = 0; tnt < NT; ++tnt) {
+      float v = acc[tnt][reg];
+      if constexpr (ADDIN) v += s16_to_f32<T16>(h[tnt]);
+      h[tnt] = f32_to_s16<T16>(v);
+    }
+    epi_put<NT>(wl, row, li, h);
+  }
+  epi_wave_sync();
+  epi_flush<T16, NT>(wl, dx, lane, roff);
 }
 
 }  // namespace
@@ -591,6 +644,13 @@ void stats_slab_reduce(at::Tensor slab, at::Tensor stats, int gx, int bnt2,
 //   the 8-cycle cadence.
 //   patch: [NR rows][Wi+2 cols][72] (stride 72: 16B-aligned b128 reads,
 //   36-dword lane stride -> worst 2-way bank conflicts).
+//   epilogue: the plain variants store one 16-bit element per lane from
+//   the accumulator. The ADDIN variant (dgrad + residual gradient) reads
+//   the addin tile with 16-byte loads into the patch LDS, adds in fp32
+//   registers, rounds once and writes whole rows with 16-byte stores
+//   (conv_epilogue.h): 32 ushort loads + 32 short stores per wave become
+//   4 + 4 dwordx4, and the kernel runs 20% faster. The same row store on
+//   the plain variants measured 2% slower, so they do not use it.
 // ---------------------------------------------------------------------------
 constexpr int PCS = 72;  // patch col stride (elements)
 
@@ -607,6 +667,8 @@ __global__ __launch_bounds__(256, 2) void conv_patch_gemm(
     const int N, const int Hi, const int Wi, const int CI, const int KO,
     const long b_row_stride, const long b_rs_stride, const int act,
     const int has_bias, const int NR) {
+  // whole-row epilogue store (conv_epilogue.h) for the ADDIN variant only
+  constexpr bool ROWST = ADDIN;
   extern __shared__ __attribute__((aligned(16))) char psmem[];
   T16* patch = reinterpret_cast<T16*>(psmem);
   T16* zstub = patch + (long)NR * (Wi + 2) * PCS;  // 72 zero elements
@@ -653,7 +715,8 @@ __global__ __launch_bounds__(256, 2) void conv_patch_gemm(
     breg[1] = *reinterpret_cast<const short8*>(wp + 8);
   };
   auto stage_b = [&]() {
-    short* pb = reinterpret_cast<short*>(ldsB + sb_n * LDK + sb_c);
+    short* pb = reinterpret_cast<short*>(
+        ldsB + (ROWST ? epi_brow<2>(sb_n) : sb_n) * LDK + sb_c);
     *reinterpret_cast<short8*>(pb) = breg[0];
     *reinterpret_cast<short8*>(pb + 8) = breg[1];
   };
@@ -743,27 +806,70 @@ __global__ __launch_bounds__(256, 2) void conv_patch_gemm(
     }
   }
 
-  // ---- epilogue: bias + act + store (+ optional BN-stats partials) ----
+  // ---- epilogue: bias + act (+ optional BN-stats partials) in fp32
+  // registers, one rounding, then the store. ch[t2]: the lane's output
+  // channel in accumulator tile t2 ----
+  const int ch[2] = {ROWST ? 2 * li : li, ROWST ? 2 * li + 1 : 32 + li};
   float bv[2];
-  bv[0] = has_bias ? bias[k0 + li] : 0.f;
-  bv[1] = has_bias ? bias[k0 + 32 + li] : 0.f;
+  bv[0] = has_bias ? bias[k0 + ch[0]] : 0.f;
+  bv[1] = has_bias ? bias[k0 + ch[1]] : 0.f;
   float ssum[2] = {}, ssq[2] = {};
+  if constexpr (ROWST) {
+    // whole rows, 16 bytes per lane: each wave brings its 32 x 64 addin
+    // tile into its own part of the patch LDS (which no tap reads any
+    // more), adds in registers, and sends the rounded tile back the same
+    // way (conv_epilogue.h)
+    using E = EpiTile<2>;
+    short* wl = reinterpret_cast<short*>(psmem) + wave * E::WAVE;
+    long roff[E::NIT];
 #pragma unroll
-  for (int reg = 0; reg < 16; ++reg) {
-    const int row = (reg & 3) + 8 * (reg >> 2) + 4 * kh;
-    const long m_out = bm0 + wm + row;
-    if (m_out < Mtot) {
+    for (int it = 0; it < E::NIT; ++it) {
+      const long m = bm0 + wm + epi_io_row<2>(it, lane);
+      roff[it] = m < Mtot ? m * KO + k0 : -1;
+    }
+    __syncthreads();  // every wave's last tap is done reading the patch
+    if constexpr (ADDIN) {
+      epi_fetch<T16, 2>(wl, addin, lane, roff);
+      epi_wave_sync();
+    }
 #pragma unroll
-      for (int t2 = 0; t2 < 2; ++t2) {
-        float v = acc[t2][reg] + bv[t2];
-        if constexpr (ADDIN)
-          v += F16<T16>::to_f32(addin[m_out * KO + k0 + t2 * 32 + li]);
-        if (act == 1) v = fmaxf(v, 0.f);
-        if (stats_slab) {
-          ssum[t2] += v;
-          ssq[t2] += v * v;
+    for (int reg = 0; reg < 16; ++reg) {
+      const int row = epi_acc_row(reg, kh);
+      short2v h = {};
+      if (bm0 + wm + row < Mtot) {
+        if constexpr (ADDIN) h = epi_get<2>(wl, row, li);
+#pragma unroll
+        for (int t2 = 0; t2 < 2; ++t2) {
+          float v = acc[t2][reg] + bv[t2];
+          if constexpr (ADDIN) v += s16_to_f32<T16>(h[t2]);
+          if (act == 1) v = fmaxf(v, 0.f);
+          if (stats_slab) {
+            ssum[t2] += v;
+            ssq[t2] += v * v;
+          }
+          h[t2] = f32_to_s16<T16>(v);
         }
-        out[m_out * KO + k0 + t2 * 32 + li] = F16<T16>::from_f32(v);
+      }
+      epi_put<2>(wl, row, li, h);
+    }
+    epi_wave_sync();
+    epi_flush<T16, 2>(wl, out, lane, roff);
+  } else {
+    // one 16-bit element per lane straight from the accumulator
+#pragma unroll
+    for (int reg = 0; reg < 16; ++reg) {
+      const long m_out = bm0 + wm + epi_acc_row(reg, kh);
+      if (m_out < Mtot) {
+#pragma unroll
+        for (int t2 = 0; t2 < 2; ++t2) {
+          float v = acc[t2][reg] + bv[t2];
+          if (act == 1) v = fmaxf(v, 0.f);
+          if (stats_slab) {
+            ssum[t2] += v;
+            ssq[t2] += v * v;
+          }
+          out[m_out * KO + k0 + ch[t2]] = F16<T16>::from_f32(v);
+        }
       }
     }
   }
@@ -776,12 +882,12 @@ __global__ __launch_bounds__(256, 2) void conv_patch_gemm(
       ssq[t2] += __shfl_xor(ssq[t2], 32, 64);
     }
     float* lsum = reinterpret_cast<float*>(psmem);  // [4 waves][128]
-    __syncthreads();
+    __syncthreads();  // patch reads / staged-tile read-back (same LDS) done
     if (kh == 0) {
 #pragma unroll
       for (int t2 = 0; t2 < 2; ++t2) {
-        lsum[wave * 128 + t2 * 32 + li] = ssum[t2];
-        lsum[wave * 128 + 64 + t2 * 32 + li] = ssq[t2];
+        lsum[wave * 128 + ch[t2]] = ssum[t2];
+        lsum[wave * 128 + 64 + ch[t2]] = ssq[t2];
       }
     }
     __syncthreads();
@@ -1901,6 +2007,8 @@ void patch_gemm_launch(bool trans, const at::Tensor& in,
   const int KO = out.size(3);
   const long M = (long)N * Hi * Wi;
   const PatchGeom pg = patch_geom(Wi);
+  TORCH_CHECK(pg.smem >= (size_t)EpiTile<2>::BYTES,
+              "patch LDS smaller than the epilogue's staged tile");
   dim3 grid((unsigned)cdiv_l(M, 128), KO / 64);
   at::Tensor slab;
   if (present(stats))

@@ -24,6 +24,7 @@
 //   fwd  : y[m, ko]   = sum_kg A_im2col[m, kg] * w24[ko, kg]
 //   wgrad: dw[ko, kg] = sum_m dy[m, ko] * A_im2col[m, kg]
 //          (transposed LDS staging, split-M chunk slabs, wgrad_reduce)
+#include "conv_epilogue.h"
 #include "conv_internal.h"
 
 typedef __attribute__((ext_vector_type(8))) _Float16 half8_s;
@@ -174,8 +175,8 @@ __global__ __launch_bounds__(256, 2) void conv_fwd_stem_gemm(
     short* pa = reinterpret_cast<short*>(lds + sa_m * SLDK + sa_c);
 #pragma unroll
     for (int i = 0; i < 4; ++i) *reinterpret_cast<short8*>(pa + 8 * i) = sa[i];
-    short* pb =
-        reinterpret_cast<short*>(lds + 128 * SLDK + sb_n * SLDK + sb_c);
+    short* pb = reinterpret_cast<short*>(lds + 128 * SLDK +
+                                         epi_brow<2>(sb_n) * SLDK + sb_c);
     *reinterpret_cast<short8*>(pb) = sb[0];
     *reinterpret_cast<short8*>(pb + 8) = sb[1];
   };
@@ -201,22 +202,34 @@ __global__ __launch_bounds__(256, 2) void conv_fwd_stem_gemm(
     }
   }
 
+  // epilogue: whole-row 16-byte stores through the wave's part of the
+  // A/B LDS (conv_epilogue.h; lane li holds channels 2*li+t)
+  using E = EpiTile<2>;
+  static_assert(sizeof(lds) >= E::BYTES, "epilogue tile must fit the A/B LDS");
+  short* wl = reinterpret_cast<short*>(lds) + wave * E::WAVE;
+  long roff[E::NIT];
+#pragma unroll
+  for (int it = 0; it < E::NIT; ++it) {
+    const long m = bm0 + wm + epi_io_row<2>(it, lane);
+    roff[it] = m < Mtot ? m * KO + k0 : -1;
+  }
   float bv[2];
-  bv[0] = has_bias ? bias[k0 + li] : 0.f;
-  bv[1] = has_bias ? bias[k0 + 32 + li] : 0.f;
+  bv[0] = has_bias ? bias[k0 + 2 * li] : 0.f;
+  bv[1] = has_bias ? bias[k0 + 2 * li + 1] : 0.f;
+  __syncthreads();  // every wave's last MFMA phase is done reading LDS
 #pragma unroll
   for (int reg = 0; reg < 16; ++reg) {
-    const int row = (reg & 3) + 8 * (reg >> 2) + 4 * kh;
-    const long m_out = bm0 + wm + row;
-    if (m_out < Mtot) {
+    short2v h;
 #pragma unroll
-      for (int t2 = 0; t2 < 2; ++t2) {
-        float v = acc[t2][reg] + bv[t2];
-        if (act == 1) v = fmaxf(v, 0.f);
-        y[m_out * KO + k0 + t2 * 32 + li] = F16<T16>::from_f32(v);
-      }
+    for (int t2 = 0; t2 < 2; ++t2) {
+      float v = acc[t2][reg] + bv[t2];
+      if (act == 1) v = fmaxf(v, 0.f);
+      h[t2] = f32_to_s16<T16>(v);
     }
+    epi_put<2>(wl, epi_acc_row(reg, kh), li, h);
   }
+  epi_wave_sync();
+  epi_flush<T16, 2>(wl, y, lane, roff);
 }
 
 // ---- forward v3: strip-staged -----------------------------------------
@@ -290,7 +303,8 @@ __global__ __launch_bounds__(256, 2) void conv_fwd_stem_strip(
   for (int e = tid * 8; e < 64 * SKG; e += 256 * 8) {
     const int row = e / SKG, col = e - row * SKG;
     *reinterpret_cast<short8*>(
-        reinterpret_cast<short*>(ldsB + row * (SKG + 8) + col)) =
+        reinterpret_cast<short*>(ldsB + epi_brow<2>(row) * (SKG + 8) +
+                                 col)) =
         *reinterpret_cast<const short8*>(w24 + (long)(k0 + row) * SKG + col);
   }
   __syncthreads();
@@ -338,27 +352,50 @@ __global__ __launch_bounds__(256, 2) void conv_fwd_stem_strip(
     acc[1] = SMfma<T16>::run(af, b1, acc[1]);
   }
 
+  // epilogue: whole-row 16-byte stores (conv_epilogue.h; lane li holds
+  // channels 2*li+t). The 3x3 strip + weights can be as small as 10.5 KB,
+  // so the waves stage 16 rows per pass (registers 0-7, then 8-15): 9 KB,
+  // which the weight tile alone covers.
+  using E = EpiTile<2, 16>;
+  short* wl = reinterpret_cast<short*>(ssmem) + wave * E::WAVE;
   float bv[2];
-  bv[0] = has_bias ? bias[k0 + li] : 0.f;
-  bv[1] = has_bias ? bias[k0 + 32 + li] : 0.f;
+  bv[0] = has_bias ? bias[k0 + 2 * li] : 0.f;
+  bv[1] = has_bias ? bias[k0 + 2 * li + 1] : 0.f;
   float ssum[2] = {}, ssq[2] = {};
   const long Mtot = (long)N * Mimg;
 #pragma unroll
-  for (int reg = 0; reg < 16; ++reg) {
-    const int row = (reg & 3) + 8 * (reg >> 2) + 4 * kh;
-    const long m_out = bm0 + wm + row;
-    if (m_out < Mtot) {
+  for (int half = 0; half < 2; ++half) {
+    long roff[E::NIT];
 #pragma unroll
-      for (int t2 = 0; t2 < 2; ++t2) {
-        float v = acc[t2][reg] + bv[t2];
-        if (act == 1) v = fmaxf(v, 0.f);
-        if (stats_slab) {
-          ssum[t2] += v;
-          ssq[t2] += v * v;
-        }
-        y[m_out * KO + k0 + t2 * 32 + li] = F16<T16>::from_f32(v);
-      }
+    for (int it = 0; it < E::NIT; ++it) {
+      const long m = bm0 + wm + half * 16 + epi_io_row<2>(it, lane);
+      roff[it] = m < Mtot ? m * KO + k0 : -1;
     }
+    if (half == 0)
+      __syncthreads();  // every wave's strip/weight reads are done
+    else
+      epi_wave_sync();  // the wave's first pass has been read back
+#pragma unroll
+    for (int r8 = 0; r8 < 8; ++r8) {
+      const int reg = half * 8 + r8;
+      const int row = epi_acc_row(reg, kh);
+      short2v h = {};
+      if (bm0 + wm + row < Mtot) {
+#pragma unroll
+        for (int t2 = 0; t2 < 2; ++t2) {
+          float v = acc[t2][reg] + bv[t2];
+          if (act == 1) v = fmaxf(v, 0.f);
+          if (stats_slab) {
+            ssum[t2] += v;
+            ssq[t2] += v * v;
+          }
+          h[t2] = f32_to_s16<T16>(v);
+        }
+      }
+      epi_put<2>(wl, row - half * 16, li, h);
+    }
+    epi_wave_sync();
+    epi_flush<T16, 2, 16>(wl, y, lane, roff);
   }
   if (stats_slab) {
     // same fold as conv_gather_gemm: kh halves by xor-shuffle, waves by
@@ -369,12 +406,12 @@ __global__ __launch_bounds__(256, 2) void conv_fwd_stem_strip(
       ssq[t2] += __shfl_xor(ssq[t2], 32, 64);
     }
     float* lsum = reinterpret_cast<float*>(ssmem);  // [4 waves][128]
-    __syncthreads();
+    __syncthreads();  // the staged tiles (same LDS) have been read back
     if (kh == 0) {
 #pragma unroll
       for (int t2 = 0; t2 < 2; ++t2) {
-        lsum[wave * 128 + t2 * 32 + li] = ssum[t2];
-        lsum[wave * 128 + 64 + t2 * 32 + li] = ssq[t2];
+        lsum[wave * 128 + 2 * li + t2] = ssum[t2];
+        lsum[wave * 128 + 64 + 2 * li + t2] = ssq[t2];
       }
     }
     __syncthreads();
@@ -598,6 +635,9 @@ static bool fwd_stem_gemm_impl(at::Tensor x, at::Tensor w, at::Tensor bias,
     const int sstride = (3 * W + 6 * (int)pad + 8 + 3) & ~3;
     const size_t smem =
         ((size_t)(nrows + 1) * sstride + 64 * (SKG + 8)) * x.element_size();
+    // (the epilogue's staged tile always fits: the weight tile alone is
+    // 64 * 72 * 2 bytes)
+    static_assert(64 * (SKG + 8) * 2 >= EpiTile<2, 16>::BYTES);
     if (smem <= 150 * 1024) {
       const bool want_stats = stats.defined() && stats.numel() > 0;
       at::Tensor slab;
