@@ -338,12 +338,12 @@ def wgradperf():
         del x, dy
 
 
-def pmcwgrad():
-    """A few 3x3 wgrad calls at the r18 b8192 layer-1 shape and nothing
-    else, for a rocprofv3 --pmc pass over whichever kernel the
-    MI355X_WGRAD_T9 knob selects."""
+def pmcwgrad(hw=32, c=64):
+    """A few 3x3 wgrad calls at one r18 b8192 layer shape (layer 1 unless
+    `pmcwgrad HW C` names another) and nothing else, for a rocprofv3 --pmc
+    pass over whichever kernel the MI355X_WGRAD_T9 knob selects."""
     import mi355x.ops as O
-    x = torch.randn(8192, 32, 32, 64, device="cuda").to(torch.bfloat16)
+    x = torch.randn(8192, hw, hw, c, device="cuda").to(torch.bfloat16)
     dy = torch.randn_like(x)
     for _ in range(6):
         O.ext().conv2d_wgrad(x, dy, 3, 3, 1, 1)
@@ -405,7 +405,7 @@ if __name__ == "__main__":
     if what == "pmcs3":
         pmcs3()
     if what == "pmcwgrad":
-        pmcwgrad()
+        pmcwgrad(*map(int, sys.argv[2:4]))
     if what == "pmcprobe":
         pmcprobe()
     if what == "r50fwd":

@@ -1468,7 +1468,8 @@ __global__ __launch_bounds__(256, SCALED ? 3 : 2) void conv_wgrad_mfma_s3(
 
 // nine-tap wgrad for 3x3/stride-1/pad-1 convs whose 64-position m-step is
 // a whole number of output rows inside one image (Wo in {8,16,32},
-// Ho*Wo % 64 == 0): ONE block computes all 9 taps of a 64(k) x 64(c) tile
+// Ho*Wo % 64 == 0), or four whole 4x4 images (below): ONE block computes
+// all 9 taps of a 64(k) x 64(c) tile
 // from ONE dy stage and ONE x stage per step, where the s3 kernel spends
 // three blocks that each stage the same dy tile and a row-shifted copy of
 // the same x rows. The x stage is the step's 64/Wo output rows plus one
@@ -1484,6 +1485,14 @@ __global__ __launch_bounds__(256, SCALED ? 3 : 2) void conv_wgrad_mfma_s3(
 // Both images use the k-minor staging map and rotate-swizzled columns of
 // the s3 kernel; the x image is 128 columns wide so the rotation wraps
 // with a mask.
+// WO == 4 (Hi == 4 too, N % 4 == 0): a step is four whole images, still in
+// natural position order. Input pixel (img, row, q) of the step sits at
+// column img*24 + (row+1)*4 + q: every image has its own zero row above and
+// below, zeroed once before the loop, so a step stages exactly its own 64
+// positions and a thread's four positions are one whole image row (the
+// q-1 / q+1 neighbours at its ends are the pad column: no lane exchange).
+// The tap's row offset r*4 is 16-byte aligned for r = 0 and 2 only; the
+// r = 1 fragment is put together from halves of those two.
 constexpr int T9CL = 128;       // x image columns (>= 64 + 2*Wo, power of 2)
 constexpr int T9LD = T9CL + 8;  // x image row length (+16B, as LDM)
 
@@ -1494,9 +1503,11 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_mfma_t9(
     float* __restrict__ dw,      // chunk slabs of [KO, 3*3*CI]
     const int Hi, const int CI, const int KO, const long Mtot,
     const long m_per_chunk) {
-  static_assert(WGM % WO == 0 && WO % 8 == 0 && 32 % WO == 0 &&
-                WGM + 2 * WO <= T9CL);
-  constexpr int NPOS = WGM + 2 * WO;  // staged input positions per step
+  constexpr bool IMG4 = WO == 4;
+  static_assert(IMG4 || (WGM % WO == 0 && WO % 8 == 0 && 32 % WO == 0 &&
+                         WGM + 2 * WO <= T9CL));
+  // staged input positions per step
+  constexpr int NPOS = IMG4 ? WGM : WGM + 2 * WO;
   __shared__ T16 lds[64 * LDM + 3 * 64 * T9LD];
   T16* const ldsX = lds + 64 * LDM;
 
@@ -1537,6 +1548,15 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_mfma_t9(
         vdy[mi] = *reinterpret_cast<const short8*>(
             dy + (m0 + sm + mi) * KO + k0 + sk);
     }
+    if constexpr (IMG4) {
+      if (do_x) {  // the step's own positions, nothing else
+        const T16* xp = x + (m0 + xpos) * CI + c0 + sk;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          vx[j] = *reinterpret_cast<const short8*>(xp + (long)j * CI);
+      }
+      return;
+    }
     if (do_x) {
       // Hi == Ho and Wi == Wo: pixel (n, p0, 0) has linear index m0, and
       // the stage's rows are contiguous from one row before it
@@ -1560,23 +1580,31 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_mfma_t9(
             reinterpret_cast<short*>(lds + (sk + e) * LDM + col)) = pk;
       }
     }
-    // every lane runs the exchange (idle lanes carry unused values)
+    int4v hl{}, hr{};
+    if constexpr (!IMG4) {
+      // every lane runs the exchange (idle lanes carry unused values)
 #pragma unroll
-    for (int j = 0; j < 4; ++j) vx[j] &= xkeep;
-    // q-1 of the first and q+1 of the last position: lane group -1 / +1 of
-    // the same wave; zero at the row ends (the pad column)
-    int4v hl = __builtin_bit_cast(int4v, vx[3]);
-    int4v hr = __builtin_bit_cast(int4v, vx[0]);
+      for (int j = 0; j < 4; ++j) vx[j] &= xkeep;
+      // q-1 of the first and q+1 of the last position: lane group -1 / +1
+      // of the same wave; zero at the row ends (the pad column)
+      hl = __builtin_bit_cast(int4v, vx[3]);
+      hr = __builtin_bit_cast(int4v, vx[0]);
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      hl[u] = __shfl_up(hl[u], 8, 64);
-      hr[u] = __shfl_down(hr[u], 8, 64);
+      for (int u = 0; u < 4; ++u) {
+        hl[u] = __shfl_up(hl[u], 8, 64);
+        hr[u] = __shfl_down(hr[u], 8, 64);
+      }
     }
     if (do_x) {
+      // WO == 4: the four positions are a whole row, both ends are pad
       const short8 zero{};
-      const short8 vl = xq > 0 ? __builtin_bit_cast(short8, hl) : zero;
-      const short8 vr = xq + 4 < WO ? __builtin_bit_cast(short8, hr) : zero;
-      const int col = (xpos + sk) & (T9CL - 1);
+      const short8 vl =
+          !IMG4 && xq > 0 ? __builtin_bit_cast(short8, hl) : zero;
+      const short8 vr =
+          !IMG4 && xq + 4 < WO ? __builtin_bit_cast(short8, hr) : zero;
+      const int col =
+          (IMG4 ? (xpos >> 4) * 24 + 4 + (xpos & 15) + sk : xpos + sk) &
+          (T9CL - 1);
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         short* row = reinterpret_cast<short*>(ldsX + (sk + e) * T9LD + col);
@@ -1589,6 +1617,19 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_mfma_t9(
       }
     }
   };
+
+  if constexpr (IMG4) {
+    // the zero rows of the four images: no stage writes them, so once
+    const int c = tid & 63;
+#pragma unroll
+    for (int h = 0; h < 24; h += 20) {
+      const int col = ((tid >> 6) * 24 + h + (c & 56)) & (T9CL - 1);
+#pragma unroll
+      for (int s = 0; s < 3; ++s)
+        *reinterpret_cast<short4v*>(reinterpret_cast<short*>(
+            ldsX + (s * 64 + c) * T9LD + col)) = short4v{};
+    }
+  }
 
   load_m(m_begin);
   for (long m0 = m_begin; m0 < m_end; m0 += WGM) {
@@ -1606,14 +1647,35 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_mfma_t9(
     for (int kk = 0; kk < WGM; kk += 16) {
       const short8 af =
           *reinterpret_cast<const short8*>(ap + ((kk + acol) & 63));
-#pragma unroll
-      for (int r = 0; r < 3; ++r) {
-        const int col = (kk + r * WO + bcol) & (T9CL - 1);
+      if constexpr (IMG4) {
+        // slice kk is image kk/16. The r = 1 fragment lies 8 bytes past the
+        // r = 0 one and 8 bytes before the r = 2 one (no wrap can fall
+        // inside it), so it is the upper half of one and the lower half of
+        // the other: no read of its own, and none that is not 16-byte
+        // aligned.
+        const int col0 = ((kk / 16) * 24 + bcol) & (T9CL - 1);
+        const int col2 = ((kk / 16) * 24 + 2 * WO + bcol) & (T9CL - 1);
 #pragma unroll
         for (int s = 0; s < 3; ++s) {
-          const short8 bf = *reinterpret_cast<const short8*>(
-              bp + s * 64 * T9LD + col);
-          acc[r * 3 + s] = Mfma32<T16>::run(af, bf, acc[r * 3 + s]);
+          const T16* bs = bp + s * 64 * T9LD;
+          const short8 b0 = *reinterpret_cast<const short8*>(bs + col0);
+          const short8 b2 = *reinterpret_cast<const short8*>(bs + col2);
+          const short8 b1 =
+              __builtin_shufflevector(b0, b2, 4, 5, 6, 7, 8, 9, 10, 11);
+          acc[s] = Mfma32<T16>::run(af, b0, acc[s]);
+          acc[3 + s] = Mfma32<T16>::run(af, b1, acc[3 + s]);
+          acc[6 + s] = Mfma32<T16>::run(af, b2, acc[6 + s]);
+        }
+      } else {
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+          const int col = (kk + r * WO + bcol) & (T9CL - 1);
+#pragma unroll
+          for (int s = 0; s < 3; ++s) {
+            const short8 bf = *reinterpret_cast<const short8*>(
+                bp + s * 64 * T9LD + col);
+            acc[r * 3 + s] = Mfma32<T16>::run(af, bf, acc[r * 3 + s]);
+          }
         }
       }
     }
@@ -1807,16 +1869,19 @@ void wgrad_s3_launch(const WgradArgs& a, int KT, WgradMode mode,
 
 // conv_wgrad_mfma_t9: one block per (k-tile, c-tile, chunk), all nine taps
 bool wgrad_t9_eligible(const WgradArgs& a) {
+  // a 64-position step is whole rows of one image, or four whole 4x4 images
+  const bool rows = (a.Wo == 8 || a.Wo == 16 || a.Wo == 32) &&
+                    (a.Ho * a.Wo) % WGM == 0;
+  const bool img4 = a.Ho == 4 && a.Wo == 4 && ((long)a.N * 16) % WGM == 0;
   return a.R == 3 && a.S == 3 && a.stride == 1 && a.pad == 1 &&
-         a.Hi == a.Ho && a.Wi == a.Wo && !a.asc &&
-         (a.Wo == 8 || a.Wo == 16 || a.Wo == 32) &&
-         (a.Ho * a.Wo) % WGM == 0 && a.KO % 64 == 0 && a.CI % 64 == 0;
+         a.Hi == a.Ho && a.Wi == a.Wo && !a.asc && (rows || img4) &&
+         a.KO % 64 == 0 && a.CI % 64 == 0;
 }
 void wgrad_t9_launch(const WgradArgs& a, const WgradSplit& sp) {
   dim3 grid(a.KO / 64, a.CI / 64, sp.nchunks);
   const long M = (long)a.N * a.Ho * a.Wo;
   DISPATCH_16(a.x, T16, {
-    pick<8, 16, 32>(a.Wo, [&](auto wo) {
+    pick<4, 8, 16, 32>(a.Wo, [&](auto wo) {
       launch256(conv_wgrad_mfma_t9<T16, decltype(wo)::value>, grid, 0,
                 (const T16*)a.x.data_ptr(), (const T16*)a.dy.data_ptr(),
                 sp.part.data_ptr<float>(), a.Hi, a.CI, a.KO, M,
@@ -1873,7 +1938,7 @@ void conv_wgrad_mfma_launch(at::Tensor x, at::Tensor dy, at::Tensor dw,
   const long M = (long)a.N * a.Ho * a.Wo;
   const long E = (long)a.KO * R * S * a.CI;
   // nine taps per block where an m-step is whole output rows of one image
-  // (MI355X_WGRAD_T9=0 restores the s3 path)
+  // or four whole 4x4 images (MI355X_WGRAD_T9=0 restores the s3 path)
   static const bool t9_on = EnvKnob("MI355X_WGRAD_T9").on();
   if (t9_on && wgrad_t9_eligible(a)) {
     // Chunk depth stays at the s3 kernel's 4096 m: with the same chunks
