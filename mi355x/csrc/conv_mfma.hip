@@ -898,6 +898,262 @@ __global__ __launch_bounds__(256, 2) void conv_patch_gemm(
   }
 }
 
+// ---------------------------------------------------------------------------
+// Ring variant of the patch kernel for the 64-channel 3x3/s1 layer
+// (CI == 64, W == 32, H % 4 == 0; fwd, dgrad, dgrad + ADDIN). At CI == 64
+// conv_patch_gemm's block lives for one patch fill and nine short taps, each
+// with its own weight stage and two barriers, and every 4-row tile fetches 6
+// input rows. Here a block stays on its CU and walks whole images
+// (blockIdx.x, + gridDim.x, ...) in steps of 128 outputs = 4 image rows:
+//   weights: the block's 64 x 576 tile is read ONCE, straight into registers
+//   (36 x 16 B per lane: the lane's own MFMA B fragments for all nine taps),
+//   so the loop has no weight stage, no weight LDS reads and no barriers for
+//   them.
+//   input: a ring of 12 image rows ([34][PCS] each, pad columns zeroed once).
+//   A step reads rows 4t-1 .. 4t+4 and only ever fetches 4 new ones: the
+//   16 KB of step t+2 are on their way into registers during all of step
+//   t-1 and step t's taps, and are written after those taps to the slot
+//   step t-1 owned. Rows outside the image are not staged; their taps read
+//   the zero stub, as in conv_patch_gemm.
+//   waves: 8, as 4 (image rows of the step) x 2 (halves of the 64 output
+//   channels), one 32x32 accumulator each; per output element the MFMAs are
+//   the same instruction in the same order (tap 0..8, kk 0..3) as in
+//   conv_patch_gemm, so results are bit-identical.
+//   epilogue: the two waves of a row share a [32][RS] staging tile (even
+//   channels from one, odd from the other) and store whole 128-byte rows;
+//   ADDIN reads its tile the same way. The 2-byte store straight from the
+//   accumulator needs 256 VGPRs and spills here, so no variant uses it.
+//   stats: one 128-float slab row per 128-output TILE, folded in
+//   conv_patch_gemm's order (registers, kh halves, then the 4 row waves).
+// Two block barriers per step.
+// ---------------------------------------------------------------------------
+constexpr int RG_W = 32;                        // image width
+constexpr int RG_ROW = (RG_W + 2) * PCS;        // elements of one ring row
+constexpr int RG_SLOTS = 3;                     // 4-row slots in the ring
+constexpr int RG_ES = EpiTile<2>::RS;           // staged output row stride
+constexpr int RG_LDS = (RG_SLOTS * 4 * RG_ROW + PCS + 4 * 32 * RG_ES) * 2 +
+                       4 * 128 * 4;             // bytes
+
+template <typename T16, bool TRANS, bool ADDIN>
+__global__ __launch_bounds__(512) void conv_patch_ring(
+    const T16* __restrict__ in,   // [N, Hi, 32, 64] (dgrad: dy)
+    const T16* __restrict__ wgt,  // fwd: [KO, 9*64]; dgrad: wflip strides
+    const float* __restrict__ bias,
+    const T16* __restrict__ addin,  // ADDIN only: out += addin
+    T16* __restrict__ out,          // [N, Hi, 32, KO]
+    float* __restrict__ stats_slab,  // null, or per-tile (sum,sumsq) rows
+    const int N, const int Hi, const int KO, const long b_row_stride,
+    const long b_rs_stride, const int act, const int has_bias) {
+  __shared__ __attribute__((aligned(16))) char rsmem[RG_LDS];
+  T16* ring = reinterpret_cast<T16*>(rsmem);  // [12 rows][34][PCS]
+  T16* zstub = ring + RG_SLOTS * 4 * RG_ROW;  // 72 zero elements
+  short* stage = reinterpret_cast<short*>(zstub + PCS);  // [4][32][RG_ES]
+  float* lsum = reinterpret_cast<float*>(stage + 4 * 32 * RG_ES);  // [4][128]
+
+  const int tid = threadIdx.x;
+  const int wave = tid >> 6;
+  const int lane = tid & 63;
+  const int li = lane & 31;  // output column (A row) and channel (B row)
+  const int kh = lane >> 5;
+  const int wr = wave >> 1;  // the step's image row this wave computes
+  const int wk = wave & 1;   // its half of the 64 output channels
+  const int k0 = blockIdx.y * 64;
+  const int G = gridDim.x;
+  const int TPI = Hi >> 2;  // steps (128-output tiles) per image
+  const int nsteps = ((N - (int)blockIdx.x + G - 1) / G) * TPI;
+
+  // zero stub and the pad columns (0 and 33) of every ring row, once: the
+  // fill only ever writes columns 1..32
+  if (tid < 64) zstub[tid] = T16{};
+  if (tid < RG_SLOTS * 4 * 2 * 8) {
+    const int row = tid >> 4, side = (tid >> 3) & 1, g8 = tid & 7;
+    *reinterpret_cast<short8*>(ring + row * RG_ROW +
+                               side * (RG_W + 1) * PCS + g8 * 8) = short8{};
+  }
+
+  // the lane's output channel within the k-tile, and its B fragments
+  const int ch = 2 * li + wk;
+  short8 bf[9][4];
+  {
+    const T16* wp = wgt + (long)(k0 + ch) * b_row_stride + kh * 8;
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap)
+#pragma unroll
+      for (int kk = 0; kk < 4; ++kk)
+        bf[tap][kk] = *reinterpret_cast<const short8*>(
+            wp + tap * b_rs_stride + kk * 16);
+  }
+  const float bv = has_bias ? bias[k0 + ch] : 0.f;
+
+  // fill: a 4-row group is 16 KB contiguous in global memory; thread `tid`
+  // moves 16-byte pieces tid and tid + 512 (rows tid/256 and tid/256 + 2)
+  const int f_dst =
+      ((tid >> 8) * (RG_W + 2) + ((tid >> 3) & 31) + 1) * PCS + (tid & 7) * 8;
+  auto group_load = [&](int n, int g, short8(&v)[2]) {
+    const T16* src = in + ((long)n * Hi + 4 * g) * (RG_W * 64) + tid * 8;
+    v[0] = *reinterpret_cast<const short8*>(src);
+    v[1] = *reinterpret_cast<const short8*>(src + 512 * 8);
+  };
+  auto ring_put = [&](int slot, const short8(&v)[2]) {
+    T16* d = ring + slot * 4 * RG_ROW + f_dst;
+    *reinterpret_cast<short8*>(d) = v[0];
+    *reinterpret_cast<short8*>(d + 2 * RG_ROW) = v[1];
+  };
+
+  // (image, group) of the block's flat step sequence, advanced by one
+  auto advance = [&](int& n, int& g) {
+    if (++g == TPI) {
+      g = 0;
+      n += G;
+    }
+  };
+  // Prefetch: pv holds the group of step it+2 while step it runs; it is
+  // fetched as soon as the group before it has left the registers for the
+  // ring, a whole step earlier. A fetch past the block's last group repeats
+  // that group (and its put lands in a slot no step reads any more), so the
+  // loop body has no branch around a load and the compiler can count the
+  // loads in flight instead of waiting for all. Two or three register sets
+  // (groups fetched two or three steps ahead) measured the same.
+  int pn = blockIdx.x, pg = 0, pleft = nsteps - 1;  // next group to fetch
+  auto fetch = [&](short8(&v)[2]) {
+    group_load(pn, pg, v);
+    if (pleft > 0) {
+      --pleft;
+      advance(pn, pg);
+    }
+  };
+  short8 pv[2];
+  for (int fg = 0; fg < 2; ++fg) {
+    fetch(pv);
+    ring_put(fg, pv);
+  }
+  fetch(pv);
+
+  // output rows this lane moves in the row store: the pair's tile is
+  // 32 rows x 128 B, each wave takes 16 rows, 8 lanes per row
+  const int io_row = wk * 16 + (lane >> 3);
+  const int io_c = (lane & 7) * 8;
+  short* st = stage + wr * 32 * RG_ES;
+  auto out_off = [&](long tile, int b) {
+    return (tile * 128 + wr * 32 + io_row + b * 8) * KO + k0 + io_c;
+  };
+  short8 av[2];  // ADDIN: the lane's pieces of the step's addin tile
+  if constexpr (ADDIN) {
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+      av[b] = *reinterpret_cast<const short8*>(
+          addin + out_off((long)blockIdx.x * TPI, b));
+  }
+
+  // The weight loads must have landed before the loop, not in it: a use
+  // here makes the compiler wait for them now. Otherwise it has to assume
+  // they may still be in flight at the loop's first MFMA and waits there,
+  // in every step, for everything in flight.
+#pragma unroll
+  for (int tap = 0; tap < 9; ++tap)
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) asm volatile("" : "+v"(bf[tap][kk]));
+  __syncthreads();
+
+  int n_img = blockIdx.x, g = 0, slot = 0;  // slot = step % 3
+  for (int it = 0; it < nsteps; ++it) {
+    const long tile = (long)n_img * TPI + g;
+    int n2 = n_img, g2 = g;  // the next step's tile (the last: itself)
+    if (it + 1 < nsteps) advance(n2, g2);
+
+    f32x16 acc = {};
+    const int prow = 4 * g + wr;
+    // the tap's A fragments (4 x 16 B per lane). Its source row is
+    // wave-uniform; outside the image -> zero stub
+    auto a_load = [&](int tap, short8(&af)[4]) {
+      const int r = tap / 3, s = tap % 3;
+      const int dr = TRANS ? 1 - r : r - 1;
+      const int dc = TRANS ? 1 - s : s - 1;
+      const bool rv = (unsigned)(prow + dr) < (unsigned)Hi;
+      int rr = slot * 4 + wr + dr;
+      rr += rr < 0 ? RG_SLOTS * 4 : 0;
+      rr -= rr >= RG_SLOTS * 4 ? RG_SLOTS * 4 : 0;
+      const T16* abase =
+          (rv ? ring + rr * RG_ROW + (li + 1 + dc) * PCS : zstub) + kh * 8;
+#pragma unroll
+      for (int kk = 0; kk < 4; ++kk)
+        af[kk] = *reinterpret_cast<const short8*>(abase + kk * 16);
+    };
+    // one tap ahead: the next tap's four reads are in flight under this
+    // tap's MFMAs (3 % faster than reading each tap where it is used)
+    short8 af[2][4];
+    a_load(0, af[0]);
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap) {
+      if (tap < 8) a_load(tap + 1, af[(tap + 1) & 1]);
+      // keep the reads up here: the scheduler otherwise sinks them to just
+      // before this tap's last MFMA
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int kk = 0; kk < 4; ++kk)
+        acc = Mfma32<T16>::run(af[tap & 1][kk], bf[tap][kk], acc);
+    }
+
+    // ---- epilogue: bias + act (+ ADDIN, + stats partials) in fp32
+    // registers, one rounding, as in conv_patch_gemm ----
+    float ssum = 0.f, ssq = 0.f;
+    if constexpr (ADDIN) {
+#pragma unroll
+      for (int b = 0; b < 2; ++b) {
+        *reinterpret_cast<short8*>(st + (io_row + b * 8) * RG_ES + io_c) =
+            av[b];
+        // the next step's tile is on its way from here on
+        av[b] = *reinterpret_cast<const short8*>(
+            addin + out_off((long)n2 * TPI + g2, b));
+      }
+    }
+    // every wave is done with this step's ring rows and with the staging
+    // tile of the previous step; the pair's addin tile is in place
+    __syncthreads();
+    ring_put(slot == 0 ? 2 : slot - 1, pv);  // group it+2
+    fetch(pv);                               // group it+3
+#pragma unroll
+    for (int reg = 0; reg < 16; ++reg) {
+      short* e = st + epi_acc_row(reg, kh) * RG_ES + ch;
+      float v = acc[reg] + bv;
+      if constexpr (ADDIN) v += s16_to_f32<T16>(*e);
+      if (act == 1) v = fmaxf(v, 0.f);
+      if (stats_slab) {
+        // conv_patch_gemm's chain, row by row: its rows are separate
+        // branches, so its v * v is fused into the running sum one row
+        // at a time. Spelled out here, where the straight-line loop
+        // would let the compiler fuse the products in another order.
+        ssum += v;
+        ssq = __builtin_fmaf(v, v, ssq);
+      }
+      *e = f32_to_s16<T16>(v);
+    }
+    if (stats_slab) {
+      ssum += __shfl_xor(ssum, 32, 64);
+      ssq += __shfl_xor(ssq, 32, 64);
+      if (kh == 0) {
+        lsum[wr * 128 + ch] = ssum;
+        lsum[wr * 128 + 64 + ch] = ssq;
+      }
+    }
+    __syncthreads();  // new ring rows, staged tile and stats rows visible
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+      *reinterpret_cast<short8*>(out + out_off(tile, b)) =
+          *reinterpret_cast<const short8*>(st + (io_row + b * 8) * RG_ES +
+                                           io_c);
+    if (stats_slab && tid < 128) {
+      float* slab =
+          stats_slab + ((long)blockIdx.y * ((long)N * TPI) + tile) * 128;
+      slab[tid] =
+          lsum[tid] + lsum[128 + tid] + lsum[256 + tid] + lsum[384 + tid];
+    }
+    n_img = n2;
+    g = g2;
+    slot = slot == 2 ? 0 : slot + 1;
+  }
+}
+
 // wgrad: dw[KO, kg] = sum_m dy[m, KO] * A_im2col[m, kg]. MFMA reduces over
 // its register-minor k dim, which here is m — both operands are m-major in
 // memory, so both tiles are staged TRANSPOSED into LDS ([k][m] / [kg][m]),
@@ -2060,8 +2316,54 @@ PatchGeom patch_geom(int W) {
   return {NR, ((size_t)NR * (W + 2) * PCS + PCS + 64 * LDK) * 2};
 }
 
+// conv_patch_ring: one block per CU (MI355X_PATCH_RING_BLOCKS overrides the
+// count), each walking images blockIdx.x, + gridDim.x, ...; the stats slab
+// has one row per 128-output tile, as conv_patch_gemm's
+void patch_ring_launch(bool trans, const at::Tensor& in,
+                       const at::Tensor& wgt, const at::Tensor& bias,
+                       const at::Tensor& addin, at::Tensor& out,
+                       const at::Tensor& stats, long b_row_stride,
+                       long b_rs_stride, long act) {
+  const int N = in.size(0), Hi = in.size(1);
+  const int KO = out.size(3);
+  static const long blocks_knob = EnvKnob("MI355X_PATCH_RING_BLOCKS").num(0);
+  const long blocks =
+      blocks_knob > 0
+          ? blocks_knob
+          : at::cuda::getCurrentDeviceProperties()->multiProcessorCount;
+  const long tiles = (long)N * Hi / 4;
+  dim3 grid((unsigned)std::min<long>(N, blocks), KO / 64);
+  at::Tensor slab;
+  if (present(stats))
+    slab = at::empty({(long)grid.y * tiles * 128},
+                     in.options().dtype(at::kFloat));
+  DISPATCH_16(in, T16, {
+    auto go = [&](auto kern) {
+      hipLaunchKernelGGL(
+          kern, grid, dim3(512), 0, cur_stream(), (const T16*)in.data_ptr(),
+          (const T16*)wgt.data_ptr(), f32_or_null(bias),
+          present(addin) ? (const T16*)addin.data_ptr() : nullptr,
+          (T16*)out.data_ptr(), f32_or_null(slab), N, Hi, KO, b_row_stride,
+          b_rs_stride, (int)act, (int)present(bias));
+    };
+    if (trans)
+      pick<true, false>(present(addin), [&](auto ADDIN) {
+        go(conv_patch_ring<T16, true, decltype(ADDIN)::value>);
+      });
+    else
+      go(conv_patch_ring<T16, false, false>);
+  });
+  if (slab.defined()) stats_slab_reduce(slab, stats, (int)tiles, 128, KO);
+}
+
+bool patch_ring_on() {
+  static const bool v = EnvKnob("MI355X_PATCH_RING").on();
+  return v;
+}
+
 // conv_patch_gemm (3x3/s1/p1, W <= 64): fwd (plain or SCALED, optional
-// stats) and dgrad (TRANS, plain or ADDIN); in/out as in gather_gemm_launch
+// stats) and dgrad (TRANS, plain or ADDIN); in/out as in gather_gemm_launch.
+// The 64-channel 32-wide layer goes to conv_patch_ring instead.
 void patch_gemm_launch(bool trans, const at::Tensor& in,
                        const at::Tensor& wgt, const at::Tensor& bias,
                        const at::Tensor& addin, const float* asc,
@@ -2070,6 +2372,12 @@ void patch_gemm_launch(bool trans, const at::Tensor& in,
                        long b_rs_stride, long act) {
   const int N = in.size(0), Hi = in.size(1), Wi = in.size(2), CI = in.size(3);
   const int KO = out.size(3);
+  if (patch_ring_on() && CI == 64 && KO % 64 == 0 && Wi == RG_W &&
+      Hi % 4 == 0 && !asc) {
+    patch_ring_launch(trans, in, wgt, bias, addin, out, stats, b_row_stride,
+                      b_rs_stride, act);
+    return;
+  }
   const long M = (long)N * Hi * Wi;
   const PatchGeom pg = patch_geom(Wi);
   TORCH_CHECK(pg.smem >= (size_t)EpiTile<2>::BYTES,
