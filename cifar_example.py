@@ -18,6 +18,11 @@ Env overrides (benchmark configs; CLI shape unchanged):
                                             (DeviceLoader) for train and test
   MI355X_AUGMENT=1                          pad-4 random crop + flip on the
                                             train loader (needs DEVICE_DATA)
+  MI355X_CLIP_NORM=<float>                  global-norm gradient clipping in
+                                            the fused step (unset or 0 = off)
+  MI355X_FP16=1 MI355X_DEVICE_SCALER=1      fp16 compute with
+                                            amp.DeviceGradScaler: dynamic loss
+                                            scaling, no host sync per step
 """
 
 import os
@@ -75,7 +80,17 @@ def main():
 
     net = build_model(os.environ.get("MI355X_MODEL", "net")).to(device)
     flat = FlatState(net)
-    optimizer = optim.SGD(flat, lr=lr, momentum=0.9)
+    clip_norm = float(os.environ.get("MI355X_CLIP_NORM", "0")) or None
+    optimizer = optim.SGD(flat, lr=lr, momentum=0.9, max_grad_norm=clip_norm)
+    dev_scaler = None
+    if os.environ.get("MI355X_DEVICE_SCALER", "0") == "1":
+        if os.environ.get("MI355X_FP16", "0") != "1":
+            raise SystemExit("MI355X_DEVICE_SCALER=1 needs MI355X_FP16=1")
+        # fp16 compute; scale, overflow check and skip decision stay on the
+        # device: no host sync in the step
+        from mi355x import amp
+        amp.set_compute_dtype(torch.float16)
+        dev_scaler = amp.DeviceGradScaler(device=device)
 
     meter = None
     if os.environ.get("MI355X_LOG_SPEED", "0") == "1":
@@ -91,8 +106,12 @@ def main():
             optimizer.zero_grad()
             outputs = net(inputs)
             loss = cross_entropy(outputs, labels)
-            loss.backward()
-            optimizer.step()
+            if dev_scaler is not None:
+                dev_scaler.scale(loss).backward()
+                optimizer.step(scaler=dev_scaler)
+            else:
+                loss.backward()
+                optimizer.step()
 
             if meter is not None:
                 meter.step(inputs.shape[0])

@@ -22,7 +22,10 @@ MI355X_SYNC_BN=1, MI355X_FP16=1 (fp16 compute + dynamic loss scaling),
 MI355X_CKPT (checkpoint path, default ./cifar_net.pth),
 MI355X_DEVICE_DATA=1 (device-resident dataset for train and test),
 MI355X_AUGMENT=1 (pad-4 random crop + flip on the train loader; needs
-MI355X_DEVICE_DATA).
+MI355X_DEVICE_DATA), MI355X_CLIP_NORM=<float> (global-norm gradient
+clipping in the fused step; unset or 0 = off), MI355X_DEVICE_SCALER=1
+(with MI355X_FP16=1: amp.DeviceGradScaler, loss scaling without a host
+sync per step).
 """
 
 import argparse
@@ -107,12 +110,21 @@ def main(args):
     # BASELINE config 5: fp16 compute + dynamic loss scaling (overflow
     # skips the step and halves the scale; clean streaks grow it)
     scaler = None
+    dev_scaler = None
     if os.environ.get("MI355X_FP16", "0") == "1":
         from mi355x import amp
         amp.set_compute_dtype(torch.float16)
-        scaler = amp.GradScaler()
+        if os.environ.get("MI355X_DEVICE_SCALER", "0") == "1":
+            # scale, overflow check and skip decision stay on the device:
+            # no host sync in the step
+            dev_scaler = amp.DeviceGradScaler(device=device)
+        else:
+            scaler = amp.GradScaler()
+    elif os.environ.get("MI355X_DEVICE_SCALER", "0") == "1":
+        raise SystemExit("MI355X_DEVICE_SCALER=1 needs MI355X_FP16=1")
+    clip_norm = float(os.environ.get("MI355X_CLIP_NORM", "0")) or None
     optimizer = optim.SGD(net.flat, lr=lr, momentum=0.9,
-                          grad_scale=net.grad_scale)
+                          grad_scale=net.grad_scale, max_grad_norm=clip_norm)
 
     meter = None
     if os.environ.get("MI355X_LOG_SPEED", "0") == "1":
@@ -136,6 +148,10 @@ def main(args):
                 if scaler.step_ok(net.flat.flat_grad):
                     optimizer.grad_scale = net.grad_scale / used
                     optimizer.step()
+            elif dev_scaler is not None:
+                dev_scaler.scale(loss).backward()
+                net.finish_grad_sync()
+                optimizer.step(scaler=dev_scaler)
             else:
                 loss.backward()
                 net.finish_grad_sync()

@@ -81,3 +81,69 @@ class GradScaler:
             self.scale_value *= self.backoff_factor
             self._clean_steps = 0
         return finite
+
+
+class DeviceGradScaler:
+    """GradScaler's dynamic loss scaling with the scale, the overflow check
+    and the skip decision all on the device: nothing in the step path reads
+    a value back, so the whole train step can be captured in a graph.
+
+        optimizer.zero_grad()
+        loss = cross_entropy(net(x), y)
+        scaler.scale(loss).backward()
+        net.finish_grad_sync()          # DDP only
+        optimizer.step(scaler=scaler)
+
+    optim.SGD.step(scaler=...) runs the inf/nan scan over the flat grad
+    buffer, folds 1/scale into the SGD kernel (which writes nothing on
+    overflow) and updates the scale by step_ok's rules, all as kernels on
+    the current stream. The optimizer's grad_scale stays the plain DDP
+    average; it must not carry 1/scale.
+
+    `state` is the one float32[8] device tensor the kernels share (layout:
+    mi355x/csrc/gradstat.hip). `scale_value` and `skipped_steps` sync and
+    are for logging.
+    """
+
+    def __init__(self, init_scale=2.0 ** 14, growth_factor=2.0,
+                 backoff_factor=0.5, growth_interval=1000, device=None):
+        from mi355x.ops import functional as _fn
+        if device is None:
+            device = "cuda" if torch.cuda.is_available() else "cpu"
+        self._fn = _fn
+        self.growth_factor = float(growth_factor)
+        self.backoff_factor = float(backoff_factor)
+        self.growth_interval = int(growth_interval)
+        self.state = _fn.new_guard_state(torch.device(device),
+                                         scale=float(init_scale))
+
+    def scale(self, loss: torch.Tensor) -> torch.Tensor:
+        return loss * self.state[self._fn.GS_SCALE]
+
+    @property
+    def scale_value(self) -> float:
+        return float(self.state[self._fn.GS_SCALE].item())
+
+    @property
+    def skipped_steps(self) -> int:
+        return int(self.state.view(torch.int32)[self._fn.GS_SKIPPED].item())
+
+    def state_dict(self):
+        ist = self.state.view(torch.int32)
+        return {"scale": self.scale_value,
+                "growth_tracker": int(ist[self._fn.GS_TRACKER].item()),
+                "skipped_steps": self.skipped_steps,
+                "growth_factor": self.growth_factor,
+                "backoff_factor": self.backoff_factor,
+                "growth_interval": self.growth_interval}
+
+    def load_state_dict(self, sd):
+        fn = self._fn
+        st = fn.new_guard_state("cpu", scale=float(sd["scale"]))
+        ist = st.view(torch.int32)
+        ist[fn.GS_TRACKER] = int(sd["growth_tracker"])
+        ist[fn.GS_SKIPPED] = int(sd["skipped_steps"])
+        self.state.copy_(st)  # in place: a captured graph keeps the tensor
+        self.growth_factor = float(sd["growth_factor"])
+        self.backoff_factor = float(sd["backoff_factor"])
+        self.growth_interval = int(sd["growth_interval"])

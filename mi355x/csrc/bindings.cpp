@@ -8,6 +8,12 @@ at::Tensor relu_bwd(at::Tensor dy, at::Tensor y);
 at::Tensor mfma_probe32(at::Tensor A, at::Tensor B);
 void sgd_step(at::Tensor p, at::Tensor g, at::Tensor m, double lr, double mu,
               double wd, double gscale);
+void grad_stats(at::Tensor g, at::Tensor slab, at::Tensor out);
+void sgd_step_guarded(at::Tensor p, at::Tensor g, at::Tensor m,
+                      at::Tensor state, double lr, double mu, double wd,
+                      double gscale, double max_norm);
+void scaler_update(at::Tensor state, double gscale, double max_norm,
+                   double growth, double backoff, long interval);
 at::Tensor cast_to_16(at::Tensor src, at::Tensor like);
 at::Tensor cast_permute_krsc(at::Tensor w, at::Tensor like);
 at::Tensor cast_permute_krsc_pad(at::Tensor w, at::Tensor like);
@@ -76,6 +82,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("relu_bwd", &relu_bwd);
   m.def("mfma_probe32", &mfma_probe32);
   m.def("sgd_step", &sgd_step);
+  m.def("grad_stats", &grad_stats);
+  m.def("sgd_step_guarded", &sgd_step_guarded);
+  m.def("scaler_update", &scaler_update);
   m.def("cast_to_16", &cast_to_16);
   m.def("cast_permute_krsc", &cast_permute_krsc);
   m.def("cast_permute_krsc_pad", &cast_permute_krsc_pad);

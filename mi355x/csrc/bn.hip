@@ -46,7 +46,7 @@ __global__ void bn_apply_kernel(const T16* __restrict__ x,
     const float sc = gamma[c] * invstd[c];
     float v = (F16<T16>::to_f32(x[t]) - mean[c]) * sc + beta[c];
     if (has_res) v += F16<T16>::to_f32(res[t]);
-    if (act == 1) v = fmaxf(v, 0.f);
+    if (act == 1) v = relu_f(v);
     y[t] = F16<T16>::from_f32(v);
   }
 }
@@ -248,7 +248,7 @@ __global__ __launch_bounds__(256) void bn_apply_fast(
     for (int u = 0; u < 8; ++u) {
       float v = s16_to_f32<T16>(vx[u]) * sc[u] + sh[u];
       if (res) v += s16_to_f32<T16>(vr[u]);
-      if (act == 1) v = fmaxf(v, 0.f);
+      if (act == 1) v = relu_f(v);
       o[u] = f32_to_s16<T16>(v);
       // mask bit mirrors the bf16-rounded "y > 0" test the backward used
       // to make by re-reading y (1/16 the bytes)

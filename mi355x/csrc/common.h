@@ -54,6 +54,15 @@ DEV_INLINE short f32_to_s16(float f) {
   return v;
 }
 
+// ReLU of every fused epilogue. Equal to fmaxf(v, 0.f) for every number
+// (-0 gives +0 too) but a NaN stays a NaN, as in torch.relu: fmaxf would
+// return 0, and an overflow that became NaN in the forward pass would then
+// train on as a clean zero where the loss scaler can never see it.
+// IEEE-754-2019 maximum: one v_maximum3_f32 on gfx950 (fmaxf is two v_max).
+DEV_INLINE float relu_f(float v) {
+  return __builtin_elementwise_maximum(v, 0.f);
+}
+
 #define CHECK_GPU(x) TORCH_CHECK((x).is_cuda(), #x " must be on GPU")
 #define CHECK_CONTIG(x) TORCH_CHECK((x).is_contiguous(), #x " must be contiguous")
 #define CHECK_16BIT(x)                                       \

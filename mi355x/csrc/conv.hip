@@ -57,7 +57,7 @@ __global__ void conv_fwd_direct(const T16* __restrict__ x,
         }
       }
     }
-    if (act == 1) acc = fmaxf(acc, 0.f);
+    if (act == 1) acc = relu_f(acc);
     y[t] = F16<T16>::from_f32(acc);
   }
 }
@@ -267,7 +267,7 @@ __global__ __launch_bounds__(256) void conv_fwd_smallc(
     float acc = bk;
 #pragma unroll
     for (int i = 0; i < S_ * S_ * C_; ++i) acc += xw[i] * wr[i];
-    if (act == 1) acc = fmaxf(acc, 0.f);
+    if (act == 1) acc = relu_f(acc);
     if (k < K) y[m * K + k] = F16<T16>::from_f32(acc);
     if (++q == Wo) {
       q = 0;
@@ -454,7 +454,7 @@ __global__ __launch_bounds__(256) void conv_fwd_stem7_lds(
       for (int u = 0; u < WPAIR; ++u)
         acc = Dot2<T16>::fma(row[u], wp[r][u], acc);
     }
-    if (act == 1) acc = fmaxf(acc, 0.f);
+    if (act == 1) acc = relu_f(acc);
     if (k < K) y[(mrow + q) * K + k] = F16<T16>::from_f32(acc);
   }
 }
@@ -501,7 +501,7 @@ __global__ __launch_bounds__(256) void conv_fwd_stem3_lds(
 #pragma unroll
       for (int i = 0; i < 9; ++i) acc += row[i] * wr[r * 9 + i];
     }
-    if (act == 1) acc = fmaxf(acc, 0.f);
+    if (act == 1) acc = relu_f(acc);
     if (k < K) y[(mrow + q) * K + k] = F16<T16>::from_f32(acc);
   }
 }

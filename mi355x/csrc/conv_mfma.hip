@@ -74,12 +74,12 @@ DEV_INLINE short8 scale8(short8 v, const Sc8& sc) {
 #pragma unroll
   for (int u = 0; u < 4; ++u) {
     const float f = s16_to_f32<T16>(v[u]) * sc.s0[u] + sc.h0[u];
-    o[u] = f32_to_s16<T16>(fmaxf(f, 0.f));
+    o[u] = f32_to_s16<T16>(relu_f(f));
   }
 #pragma unroll
   for (int u = 0; u < 4; ++u) {
     const float f = s16_to_f32<T16>(v[4 + u]) * sc.s1[u] + sc.h1[u];
-    o[4 + u] = f32_to_s16<T16>(fmaxf(f, 0.f));
+    o[4 + u] = f32_to_s16<T16>(relu_f(f));
   }
   return o;
 }
@@ -332,7 +332,7 @@ __global__ __launch_bounds__(256, 2) void conv_gather_gemm(
       for (int tnt = 0; tnt < NT; ++tnt) {
         float v = acc[tnt][reg] + bv[tnt];
         if constexpr (ADDIN) v += s16_to_f32<T16>(h[tnt]);
-        if (act == 1) v = fmaxf(v, 0.f);
+        if (act == 1) v = relu_f(v);
         if (stats_slab) {
           ssum[tnt] += v;
           ssq[tnt] += v * v;
@@ -842,7 +842,7 @@ __global__ __launch_bounds__(256, 2) void conv_patch_gemm(
         for (int t2 = 0; t2 < 2; ++t2) {
           float v = acc[t2][reg] + bv[t2];
           if constexpr (ADDIN) v += s16_to_f32<T16>(h[t2]);
-          if (act == 1) v = fmaxf(v, 0.f);
+          if (act == 1) v = relu_f(v);
           if (stats_slab) {
             ssum[t2] += v;
             ssq[t2] += v * v;
@@ -863,7 +863,7 @@ __global__ __launch_bounds__(256, 2) void conv_patch_gemm(
 #pragma unroll
         for (int t2 = 0; t2 < 2; ++t2) {
           float v = acc[t2][reg] + bv[t2];
-          if (act == 1) v = fmaxf(v, 0.f);
+          if (act == 1) v = relu_f(v);
           if (stats_slab) {
             ssum[t2] += v;
             ssq[t2] += v * v;
@@ -1117,7 +1117,7 @@ __global__ __launch_bounds__(512) void conv_patch_ring(
       short* e = st + epi_acc_row(reg, kh) * RG_ES + ch;
       float v = acc[reg] + bv;
       if constexpr (ADDIN) v += s16_to_f32<T16>(*e);
-      if (act == 1) v = fmaxf(v, 0.f);
+      if (act == 1) v = relu_f(v);
       if (stats_slab) {
         // conv_patch_gemm's chain, row by row: its rows are separate
         // branches, so its v * v is fused into the running sum one row

@@ -34,7 +34,7 @@ __global__ void linear_fwd_kernel(const T16* __restrict__ x,
       for (; k < K; ++k)
         acc += F16<T16>::to_f32(xp[k]) * F16<T16>::to_f32(wp[k]);
     }
-    if (act == 1) acc = fmaxf(acc, 0.f);
+    if (act == 1) acc = relu_f(acc);
     y[t] = F16<T16>::from_f32(acc);
   }
 }

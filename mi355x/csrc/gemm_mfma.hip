@@ -131,7 +131,7 @@ __global__ __launch_bounds__(256, 2) void gemm_mfma_kernel(
         const int n = n0 + t2 * 32 + li;
         if (n < N) {
           float v = acc[t2][reg] + bv[t2];
-          if (act == 1) v = fmaxf(v, 0.f);
+          if (act == 1) v = relu_f(v);
           if (OUT32)
             reinterpret_cast<float*>(out)[m_out * (long)N + n] = v;
           else

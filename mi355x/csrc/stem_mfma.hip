@@ -223,7 +223,7 @@ __global__ __launch_bounds__(256, 2) void conv_fwd_stem_gemm(
 #pragma unroll
     for (int t2 = 0; t2 < 2; ++t2) {
       float v = acc[t2][reg] + bv[t2];
-      if (act == 1) v = fmaxf(v, 0.f);
+      if (act == 1) v = relu_f(v);
       h[t2] = f32_to_s16<T16>(v);
     }
     epi_put<2>(wl, epi_acc_row(reg, kh), li, h);
@@ -384,7 +384,7 @@ __global__ __launch_bounds__(256, 2) void conv_fwd_stem_strip(
 #pragma unroll
         for (int t2 = 0; t2 < 2; ++t2) {
           float v = acc[t2][reg] + bv[t2];
-          if (act == 1) v = fmaxf(v, 0.f);
+          if (act == 1) v = relu_f(v);
           if (stats_slab) {
             ssum[t2] += v;
             ssq[t2] += v * v;

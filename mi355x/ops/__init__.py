@@ -6,7 +6,10 @@ from .functional import (  # noqa: F401
     cross_entropy,
     gather_augment,
     global_avg_pool,
+    grad_stats,
     linear,
     max_pool2d,
+    scaler_update,
     sgd_step,
+    sgd_step_guarded,
 )

@@ -667,3 +667,122 @@ def sgd_step(flat_param, flat_grad, flat_momentum, lr, momentum,
         g = g.add(flat_param, alpha=weight_decay)
     flat_momentum.mul_(momentum).add_(g)
     flat_param.add_(flat_momentum, alpha=-lr)
+
+
+# ---------------------------------------------------------------------------
+# guarded optimizer step: global-norm clipping + device-side loss scaling
+# ---------------------------------------------------------------------------
+
+# Guard state: one float32[8] tensor (layout: mi355x/csrc/gradstat.hip).
+# The integer fields hold int32 bit patterns: read them through
+# state.view(torch.int32).
+GS_SCALE, GS_INV_SCALE, GS_TRACKER, GS_SKIPPED = 0, 1, 2, 3
+GS_NONFINITE, GS_RAW_NORM, GS_LAST_NORM, GS_LAST_COEF = 4, 5, 6, 7
+GS_LEN = 8
+GRAD_STATS_SLAB = 2 * 2048  # floats: per-block sums of squares, then counts
+
+
+def new_guard_state(device, scale=1.0):
+    """A fresh guard state: the given loss scale, every counter zero."""
+    st = torch.zeros(GS_LEN, dtype=torch.float32)
+    st[GS_SCALE] = scale
+    st[GS_INV_SCALE] = 1.0 / scale
+    st[GS_LAST_COEF] = 1.0
+    return st.to(device)
+
+
+def grad_stats(flat_grad, slab=None, out=None):
+    """L2 norm and inf/nan element count of the flat fp32 grad buffer, left
+    on the device: returns (norm 0-d float32, count 0-d int32), views of
+    ``out`` (float32[2]: count bits, norm; allocated if None).
+
+    GPU: one pass of per-block partials into ``slab`` (float32
+    [GRAD_STATS_SLAB], allocated if None), then a fixed-order one-block
+    combine in double, so two calls on one buffer agree bit for bit. An
+    element counts as non-finite by its own exponent bits (a finite value
+    whose square overflows does not), like ``torch.isfinite``."""
+    if out is None:
+        out = torch.empty(2, dtype=torch.float32, device=flat_grad.device)
+    if flat_grad.is_cuda:
+        if slab is None:
+            slab = torch.empty(GRAD_STATS_SLAB, dtype=torch.float32,
+                               device=flat_grad.device)
+        ext().grad_stats(flat_grad, slab, out)
+    else:
+        iout = out.view(torch.int32)
+        iout[0] = (~torch.isfinite(flat_grad)).sum().clamp(max=2**31 - 1)
+        out[1] = flat_grad.double().square().sum().sqrt()
+    return out[1], out.view(torch.int32)[0]
+
+
+def _guard_coef(state, grad_scale, max_norm):
+    """(norm, coef, eff) as float32 0-d tensors — gradstat.hip's guard_coef."""
+    k = state[GS_INV_SCALE] * torch.tensor(grad_scale, dtype=torch.float32,
+                                           device=state.device)
+    norm = state[GS_RAW_NORM] * k
+    if max_norm == float("inf"):
+        coef = torch.ones_like(norm)
+    else:
+        # fminf semantics: a nan quotient (skipped step anyway) gives 1
+        q = torch.tensor(max_norm, dtype=torch.float32,
+                         device=state.device) / (norm + 1e-6)
+        coef = torch.where(q < 1.0, q, torch.ones_like(q))
+    return norm, coef, k * coef
+
+
+def sgd_step_guarded(flat_param, flat_grad, flat_momentum, state, lr,
+                     momentum, weight_decay=0.0, grad_scale=1.0,
+                     max_norm=float("inf")):
+    """sgd_step with the gradient multiplier taken from the guard ``state``
+    that grad_stats filled (state[4:6]):
+
+        norm = raw_norm * grad_scale * inv_scale   (the true gradient's norm)
+        coef = min(1, max_norm / (norm + 1e-6))    (1 if max_norm is inf)
+        g_eff = g * (grad_scale * inv_scale * coef) + wd * p
+
+    and nothing written at all if the gradient holds an inf/nan. No host
+    sync on the GPU. With inv_scale == 1 and max_norm == inf this is
+    sgd_step bit for bit."""
+    max_norm = float(max_norm)
+    if flat_param.is_cuda:
+        ext().sgd_step_guarded(flat_param, flat_grad, flat_momentum, state,
+                               lr, momentum, weight_decay, grad_scale,
+                               max_norm)
+        return
+    if int(state.view(torch.int32)[GS_NONFINITE]) != 0:
+        return
+    _, _, eff = _guard_coef(state, grad_scale, max_norm)
+    g = flat_grad.mul(eff)
+    if weight_decay != 0.0:
+        g = g.add(flat_param, alpha=weight_decay)
+    flat_momentum.mul_(momentum).add_(g)
+    flat_param.add_(flat_momentum, alpha=-lr)
+
+
+def scaler_update(state, grad_scale=1.0, max_norm=float("inf"),
+                  growth_factor=2.0, backoff_factor=0.5, growth_interval=0):
+    """After sgd_step_guarded: GradScaler.step_ok's rules applied to the
+    guard state on the device. Overflow: scale *= backoff, tracker = 0,
+    skipped += 1. Clean: tracker += 1, and at growth_interval scale *= growth,
+    tracker = 0. growth_interval <= 0 keeps the scale (clip-only use). Also
+    stores the step's norm and clip coefficient for logging."""
+    max_norm = float(max_norm)
+    if state.is_cuda:
+        ext().scaler_update(state, grad_scale, max_norm, growth_factor,
+                            backoff_factor, int(growth_interval))
+        return
+    norm, coef, _ = _guard_coef(state, grad_scale, max_norm)
+    ist = state.view(torch.int32)
+    if int(ist[GS_NONFINITE]) != 0:
+        ist[GS_SKIPPED] += 1
+        if growth_interval > 0:
+            state[GS_SCALE] *= backoff_factor
+            ist[GS_TRACKER] = 0
+    elif growth_interval > 0:
+        ist[GS_TRACKER] += 1
+        if int(ist[GS_TRACKER]) >= growth_interval:
+            state[GS_SCALE] *= growth_factor
+            ist[GS_TRACKER] = 0
+    state[GS_INV_SCALE] = 1.0 / state[GS_SCALE]
+    state[GS_LAST_NORM] = norm
+    state[GS_LAST_COEF] = coef

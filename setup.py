@@ -17,6 +17,7 @@ from torch.utils.cpp_extension import BuildExtension, CUDAExtension  # noqa: E40
 SRC = [
     "mi355x/csrc/bindings.cpp",
     "mi355x/csrc/elementwise.hip",
+    "mi355x/csrc/gradstat.hip",
     "mi355x/csrc/augment.hip",
     "mi355x/csrc/conv.hip",
     "mi355x/csrc/conv_mfma.hip",
