@@ -1154,6 +1154,351 @@ __global__ __launch_bounds__(512) void conv_patch_ring(
   }
 }
 
+// ---------------------------------------------------------------------------
+// Streaming variant of the patch kernel for the 128/256/512-channel 3x3/s1
+// layers (CI % 64 == 0, CI >= 128, W in {4, 8, 16}; fwd, dgrad, dgrad +
+// ADDIN). conv_patch_gemm's block lives for CI/64 c-chunks; each is a patch
+// fill behind a barrier and nine weight-tile stages behind two barriers each
+// (20 barriers for 72 MFMAs per wave), and every 128-output block re-stages
+// the k-tile's weights. Here one 512-thread block per CU keeps one 64-channel
+// output tile (k-tile) and walks m-tiles of 256 outputs (its rank, + blocks
+// of that k-tile, ...) as ONE flat sequence of stages (m-tile, c-chunk):
+//   operands of a stage: the input patch of the 256 outputs ([256/W + 2
+//   rows][W + 2][PCS], pad columns zeroed once) and the whole 64 x 9 x 64
+//   weight slice ([9][64][LDK]). Those of stage i+1 are requested (14
+//   global_load_dwordx4 per thread, into registers) right after stage i's
+//   operands are in LDS, travel during its 72 MFMAs per wave, and are written
+//   to LDS between the two barriers that separate the stages. Whether i+1 is
+//   the next c-chunk or the next m-tile makes no difference. The fetch after
+//   the block's last stage repeats it and is never written.
+//   waves: 2 groups x 4; a group owns a 128-output half, a wave 32 m x 64 k
+//   as two 32x32 accumulators: conv_patch_gemm's wave tile, and per output
+//   element the same MFMAs in the same order (c-chunk, tap 0..8, kk 0..3),
+//   so results are bit-identical.
+//   epilogue: runs after the NEXT stage's operands are in LDS and the stage
+//   after that is requested, so its stores are not waited for until a whole
+//   stage later. Each wave stages 16 rows at a time in a private tile and
+//   stores whole 128-byte rows (conv_epilogue.h); the ADDIN tile is requested
+//   a stage ahead and arrives through the same tile.
+//   stats: one 128-float slab row per 128-output half, folded in
+//   conv_patch_gemm's order (registers, kh halves, the group's 4 waves).
+// Two block barriers per stage. W divides 256, so every tile starts at the
+// beginning of an image row; vertical pad, image changes inside a tile and
+// the M tail are a per-lane address select onto the zero stub. Patch rows
+// outside the tensor hold a clamped (valid) address's data; no lane with a
+// valid output reads them.
+// LDS (bytes): weights 82,944 + stub 144 + staging 8 x 2,304 = 18,432 + stats
+// rows 4,096 = 105,616, + patch 46,656 (W = 16), 48,960 (W = 8) or 57,024
+// (W = 4): 152,272 / 154,576 / 162,640 of 163,840. Declared for W = 4.
+// ---------------------------------------------------------------------------
+constexpr int ST_M = 256;                              // outputs per m-tile
+constexpr int ST_WIMG = 9 * 64 * LDK;                  // weight image, elements
+constexpr int ST_PATCH = (ST_M / 4 + 2) * (4 + 2) * PCS;  // W = 4: the largest
+constexpr int ST_EPI = EpiTile<2, 16>::WAVE;           // a wave's staging tile
+constexpr int ST_LDS =
+    (ST_PATCH + PCS + ST_WIMG + 8 * ST_EPI) * 2 + 8 * 128 * 4;  // bytes
+static_assert(ST_LDS <= 160 * 1024, "conv_patch_stream: LDS over 160 KiB");
+
+template <typename T16, bool TRANS, bool ADDIN>
+__global__ __launch_bounds__(512) void conv_patch_stream(
+    const T16* __restrict__ in,   // [N, Hi, W, CI] (dgrad: dy)
+    const T16* __restrict__ wgt,  // fwd: [KO, 9*CI]; dgrad: wflip strides
+    const float* __restrict__ bias,
+    const T16* __restrict__ addin,  // ADDIN only: out += addin
+    T16* __restrict__ out,          // [N, Hi, W, KO]
+    float* __restrict__ stats_slab,  // null, or per-half (sum,sumsq) rows
+    const int N, const int Hi, const int lw /* log2 W */, const int CI,
+    const int KO, const long b_row_stride, const long b_rs_stride,
+    const int act, const int has_bias, const int xcd_local) {
+  using E = EpiTile<2, 16>;
+  __shared__ __attribute__((aligned(16))) char ssmem[ST_LDS];
+  const int W = 1 << lw;
+  T16* wimg = reinterpret_cast<T16*>(ssmem);  // [9][64][LDK]
+  T16* zstub = wimg + ST_WIMG;                // 72 zero elements
+  short* stage = reinterpret_cast<short*>(zstub + PCS);  // [8][16][E::RS]
+  float* lsum = reinterpret_cast<float*>(stage + 8 * ST_EPI);  // [8][128]
+  T16* patch = reinterpret_cast<T16*>(lsum + 8 * 128);
+
+  const int tid = threadIdx.x;
+  const int wave = tid >> 6;
+  const int lane = tid & 63;
+  const int li = lane & 31;
+  const int kh = lane >> 5;
+  const int wm = wave * 32;  // the wave's m-rows within the tile
+
+  // k-tile and rank of this block among the blocks of its k-tile. Blocks b
+  // and b + 8 share an XCD: with xcd_local the blocks of a k-tile sit on as
+  // few XCDs as possible, so its weights stay in their L2s (speed only).
+  const int KT = KO / 64;
+  const int cnt = gridDim.x / KT;  // the host makes the grid a multiple
+  int ky, rank;
+  if (xcd_local) {
+    ky = ((int)blockIdx.x & 7) % KT;
+    rank = ((int)blockIdx.x >> 3) * (8 / KT) + ((int)blockIdx.x & 7) / KT;
+  } else {
+    ky = (int)blockIdx.x % KT;
+    rank = (int)blockIdx.x / KT;
+  }
+  const int k0 = ky * 64;
+  const long Mtot = (long)N * Hi * W;
+  const int MT = (int)((Mtot + ST_M - 1) / ST_M);
+  const int cchunks = CI / BK;
+  const int ntiles = rank < MT ? (MT - rank + cnt - 1) / cnt : 0;
+  const int nstages = ntiles * cchunks;
+  if (nstages == 0) return;
+
+  // zero stub and the pad columns (0 and W + 1) of every patch row, once:
+  // the fill only ever writes columns 1..W
+  const int NR = (ST_M >> lw) + 2;
+  if (tid < 64) zstub[tid] = T16{};
+  for (int i = tid; i < NR * 16; i += 512) {
+    const int row = i >> 4, side = (i >> 3) & 1, g8 = i & 7;
+    *reinterpret_cast<short8*>(patch + (row * (W + 2) + side * (W + 1)) * PCS +
+                               g8 * 8) = short8{};
+  }
+
+  // ---- operand fetch: thread `tid` moves, per tap, the 16-byte piece
+  // (weight row tid/8, channels (tid%8)*8..) and five pieces of the patch
+  // (pixel tid/8 + 64 b of the tile's NR * W, same channels) ----
+  const int f_n = tid >> 3, f_c = (tid & 7) * 8;
+  const T16* wsrc = wgt + (long)(k0 + f_n) * b_row_stride + f_c;
+  const int w_dst = epi_brow<2>(f_n) * LDK + f_c;
+  const int p_dst = ((f_n >> lw) * (W + 2) + (f_n & (W - 1)) + 1) * PCS + f_c;
+  const int p_step = (64 >> lw) * (W + 2) * PCS;  // 64 pixels further
+  const bool p_tail = f_n < 2 * W;  // piece 4 exists (NR * W = 256 + 2 W)
+  short8 wv[9], pv[5];
+  auto fetch = [&](long m0, int cc) {
+    const T16* wp = wsrc + cc * BK;
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap)
+      wv[tap] = *reinterpret_cast<const short8*>(wp + tap * b_rs_stride);
+    const T16* ip = in + cc * BK + f_c;
+#pragma unroll
+    for (int b = 0; b < 5; ++b) {
+      // pixel of the tensor, clamped into it: always loadable
+      long px = m0 - W + f_n + 64 * b;
+      px = px < 0 ? 0 : px;
+      px = px < Mtot ? px : Mtot - 1;
+      pv[b] = *reinterpret_cast<const short8*>(ip + px * CI);
+    }
+  };
+  auto put = [&]() {
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap)
+      *reinterpret_cast<short8*>(wimg + tap * 64 * LDK + w_dst) = wv[tap];
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+      *reinterpret_cast<short8*>(patch + p_dst + b * p_step) = pv[b];
+    if (p_tail) *reinterpret_cast<short8*>(patch + p_dst + 4 * p_step) = pv[4];
+  };
+  // the block's flat stage sequence; the fetch past its end repeats the
+  // last stage, so no load sits behind a branch
+  int f_t = rank, f_cc = 0, f_left = nstages - 1;
+  auto fetch_next = [&]() {
+    fetch((long)f_t * ST_M, f_cc);
+    if (f_left > 0) {
+      --f_left;
+      if (++f_cc == cchunks) {
+        f_cc = 0;
+        f_t += cnt;
+      }
+    }
+  };
+
+  // ---- per-lane A coordinates: fixed within the tile, since every tile
+  // starts at the beginning of an image row ----
+  const int prow = ((wm + li) >> lw) + 1;
+  const int pcol = ((wm + li) & (W - 1)) + 1;
+  const T16* a_lane = patch + (prow * (W + 2) + pcol) * PCS + kh * 8;
+  const T16* a_zero = zstub + kh * 8;
+  const T16* b_lane = wimg + li * LDK + kh * 8;
+
+  // ---- epilogue of one m-tile: bias + act (+ ADDIN, + stats partials) in
+  // fp32 registers, one rounding, as in conv_patch_gemm ----
+  const int ch0 = 2 * li;  // the lane's channels: ch0 (acc[0]), ch0 + 1
+  float bv[2];
+  bv[0] = has_bias ? bias[k0 + ch0] : 0.f;
+  bv[1] = has_bias ? bias[k0 + ch0 + 1] : 0.f;
+  short* wl = stage + wave * ST_EPI;
+  const int io_row = lane >> 3, io_c = (lane & 7) * 8;
+  short8 av[2][E::NIT];  // ADDIN: the lane's pieces of the tile's addin rows
+  auto addin_load = [&](long m0) {
+#pragma unroll
+    for (int half = 0; half < 2; ++half)
+#pragma unroll
+      for (int it = 0; it < E::NIT; ++it) {
+        long m = m0 + wm + half * 16 + it * E::RPI + io_row;
+        m = m < Mtot ? m : Mtot - 1;  // rows past the end are never used
+        av[half][it] =
+            *reinterpret_cast<const short8*>(addin + m * KO + k0 + io_c);
+      }
+  };
+  f32x16 acc[2] = {};
+  auto epilogue = [&](long m0) {
+    const long bm = m0 + wm;
+    float ssum[2] = {}, ssq[2] = {};
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+      long roff[E::NIT];
+#pragma unroll
+      for (int it = 0; it < E::NIT; ++it) {
+        const long m = bm + half * 16 + epi_io_row<2>(it, lane);
+        roff[it] = m < Mtot ? m * KO + k0 : -1;
+      }
+      epi_wave_sync();  // the wave's previous pass has been read back
+      if constexpr (ADDIN) {
+#pragma unroll
+        for (int it = 0; it < E::NIT; ++it)
+          *reinterpret_cast<short8*>(wl + epi_io_row<2>(it, lane) * E::RS +
+                                     io_c) = av[half][it];
+        epi_wave_sync();
+      }
+#pragma unroll
+      for (int r8 = 0; r8 < 8; ++r8) {
+        const int reg = half * 8 + r8;
+        const int row = epi_acc_row(reg, kh);
+        short2v h = {};
+        if (bm + row < Mtot) {
+          if constexpr (ADDIN) h = epi_get<2>(wl, row - half * 16, li);
+#pragma unroll
+          for (int t2 = 0; t2 < 2; ++t2) {
+            float v = acc[t2][reg] + bv[t2];
+            if constexpr (ADDIN) v += s16_to_f32<T16>(h[t2]);
+            if (act == 1) v = relu_f(v);
+            if (stats_slab) {
+              // conv_patch_gemm's chain: v * v fused into the running sum
+              // row by row (see conv_patch_ring)
+              ssum[t2] += v;
+              ssq[t2] = __builtin_fmaf(v, v, ssq[t2]);
+            }
+            h[t2] = f32_to_s16<T16>(v);
+          }
+        }
+        epi_put<2>(wl, row - half * 16, li, h);
+      }
+      epi_wave_sync();
+      epi_flush<T16, 2, 16>(wl, out, lane, roff);
+    }
+    if (stats_slab) {
+#pragma unroll
+      for (int t2 = 0; t2 < 2; ++t2) {
+        ssum[t2] += __shfl_xor(ssum[t2], 32, 64);
+        ssq[t2] += __shfl_xor(ssq[t2], 32, 64);
+      }
+      if (kh == 0) {
+#pragma unroll
+        for (int t2 = 0; t2 < 2; ++t2) {
+          lsum[wave * 128 + ch0 + t2] = ssum[t2];
+          lsum[wave * 128 + 64 + ch0 + t2] = ssq[t2];
+        }
+      }
+    }
+  };
+  // the slab rows of a tile whose epilogue every wave has finished (a block
+  // barrier lies between): one row per 128-output half that exists
+  const long nt128 = (Mtot + 127) / 128;
+  auto slab_write = [&](long tile) {
+    if (tid < 256) {
+      const int g2 = tid >> 7, t = tid & 127;
+      const long row = tile * 2 + g2;
+      const float* l = lsum + g2 * 4 * 128 + t;
+      if (row < nt128)
+        stats_slab[((long)ky * nt128 + row) * 128 + t] =
+            l[0] + l[128] + l[256] + l[384];
+    }
+  };
+
+  fetch_next();  // stage 0
+
+  int tile = rank, cc = 0;
+  long e_tile = -1;  // the tile whose epilogue is still to run
+  bool s_pend = false;  // lsum holds e_tile's partials, slab not written
+  long s_tile = 0;
+  for (int s = 0; s < nstages; ++s) {
+    const long m0 = (long)tile * ST_M;
+    __syncthreads();  // every wave is done with the previous stage's LDS
+    put();
+    if (stats_slab && s_pend) {
+      slab_write(s_tile);
+      s_pend = false;
+    }
+    __syncthreads();  // operands (and, at s == 0, the zeroed pads) visible
+    fetch_next();  // stage s + 1
+    if (e_tile >= 0) {
+      epilogue(e_tile * ST_M);
+      if (stats_slab) {
+        s_pend = true;
+        s_tile = e_tile;
+      }
+      e_tile = -1;
+#pragma unroll
+      for (int t2 = 0; t2 < 2; ++t2)
+#pragma unroll
+        for (int reg = 0; reg < 16; ++reg) acc[t2][reg] = 0.f;
+    }
+    if constexpr (ADDIN) {
+      // this tile's addin rows, for the epilogue a stage from now
+      if (cc == cchunks - 1) addin_load(m0);
+    }
+
+    // tap-row validity is per lane, constant over s and kk
+    const long m_lane = m0 + wm + li;
+    const int p_lane = (int)((m_lane >> lw) % Hi);
+    const bool m_ok = m_lane < Mtot;
+    // One flat sequence of 36 steps (tap, kk), each one A and two B
+    // fragments and two MFMAs. The reads of step i + 2 are issued before the
+    // MFMAs of step i (three fragment sets), so an MFMA never waits for a
+    // read the wave has just issued; the scheduling barriers keep the
+    // compiler from moving the reads back to their use.
+    struct Frag {
+      short8 a, b0, b1;
+    };
+    constexpr int PD = 2;  // steps ahead
+    Frag fr[PD + 1];
+    auto frag_load = [&](int st, Frag& f) {
+      const int tap = st >> 2, kk = st & 3;
+      const int r = tap / 3, sx = tap % 3;
+      const int dr = TRANS ? 1 - r : r - 1;
+      const int dc = TRANS ? 1 - sx : sx - 1;
+      const bool rv = m_ok && (unsigned)(p_lane + dr) < (unsigned)Hi;
+      const T16* abase = rv ? a_lane + (dr * (W + 2) + dc) * PCS : a_zero;
+      const T16* bt = b_lane + tap * 64 * LDK + kk * 16;
+      f.a = *reinterpret_cast<const short8*>(abase + kk * 16);
+      f.b0 = *reinterpret_cast<const short8*>(bt);
+      f.b1 = *reinterpret_cast<const short8*>(bt + 32 * LDK);
+    };
+#pragma unroll
+    for (int st = 0; st < PD; ++st) frag_load(st, fr[st]);
+#pragma unroll
+    for (int st = 0; st < 36; ++st) {
+      if (st + PD < 36) frag_load(st + PD, fr[(st + PD) % (PD + 1)]);
+      __builtin_amdgcn_sched_barrier(0);
+      const Frag& f = fr[st % (PD + 1)];
+      acc[0] = Mfma32<T16>::run(f.a, f.b0, acc[0]);
+      acc[1] = Mfma32<T16>::run(f.a, f.b1, acc[1]);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+
+    if (++cc == cchunks) {
+      cc = 0;
+      e_tile = tile;
+      tile += cnt;
+    }
+  }
+  // the last tile. With one c-chunk per tile the tile before it still has
+  // its partials in lsum here (block-uniform condition)
+  if (stats_slab && s_pend) {
+    __syncthreads();
+    slab_write(s_tile);
+    __syncthreads();
+  }
+  epilogue(e_tile * ST_M);
+  if (stats_slab) {
+    __syncthreads();
+    slab_write(e_tile);
+  }
+}
+
 // wgrad: dw[KO, kg] = sum_m dy[m, KO] * A_im2col[m, kg]. MFMA reduces over
 // its register-minor k dim, which here is m — both operands are m-major in
 // memory, so both tiles are staged TRANSPOSED into LDS ([k][m] / [kg][m]),
@@ -2361,9 +2706,69 @@ bool patch_ring_on() {
   return v;
 }
 
+// conv_patch_stream: one block per CU (MI355X_PATCH_STREAM_BLOCKS overrides
+// the count; it is rounded down to a multiple of the KO/64 k-tiles, at
+// least one block each). The blocks of a k-tile share its m-tiles of 256
+// outputs; the stats slab has one row per 128-output tile, as
+// conv_patch_gemm's.
+void patch_stream_launch(bool trans, const at::Tensor& in,
+                         const at::Tensor& wgt, const at::Tensor& bias,
+                         const at::Tensor& addin, at::Tensor& out,
+                         const at::Tensor& stats, long b_row_stride,
+                         long b_rs_stride, long act) {
+  const int N = in.size(0), Hi = in.size(1), Wi = in.size(2), CI = in.size(3);
+  const int KO = out.size(3);
+  static const long blocks_knob =
+      EnvKnob("MI355X_PATCH_STREAM_BLOCKS").num(0);
+  const long blocks =
+      blocks_knob > 0
+          ? blocks_knob
+          : at::cuda::getCurrentDeviceProperties()->multiProcessorCount;
+  const long M = (long)N * Hi * Wi;
+  const long KT = KO / 64;
+  const long MT = cdiv_l(M, ST_M);
+  const long G = std::max(KT, std::min(MT * KT, blocks) / KT * KT);
+  // blocks b and b + 8 share an XCD: where the counts allow it, a k-tile's
+  // blocks are kept on as few XCDs as possible (the kernel's rank mapping)
+  const bool xcd_local = G % 8 == 0 && 8 % KT == 0;
+  int lw = 0;
+  while ((1 << lw) < Wi) ++lw;
+  const long nt128 = cdiv_l(M, 128);
+  at::Tensor slab;
+  if (present(stats))
+    slab = at::empty({KT * nt128 * 128}, in.options().dtype(at::kFloat));
+  DISPATCH_16(in, T16, {
+    auto go = [&](auto kern) {
+      hipLaunchKernelGGL(
+          kern, dim3((unsigned)G), dim3(512), 0, cur_stream(),
+          (const T16*)in.data_ptr(), (const T16*)wgt.data_ptr(),
+          f32_or_null(bias),
+          present(addin) ? (const T16*)addin.data_ptr() : nullptr,
+          (T16*)out.data_ptr(), f32_or_null(slab), N, Hi, lw, CI, KO,
+          b_row_stride, b_rs_stride, (int)act, (int)present(bias),
+          (int)xcd_local);
+    };
+    if (trans)
+      pick<true, false>(present(addin), [&](auto ADDIN) {
+        go(conv_patch_stream<T16, true, decltype(ADDIN)::value>);
+      });
+    else
+      go(conv_patch_stream<T16, false, false>);
+  });
+  if (slab.defined()) stats_slab_reduce(slab, stats, (int)nt128, 128, KO);
+}
+
+bool patch_stream_on() {
+  static const bool v = EnvKnob("MI355X_PATCH_STREAM").on();
+  return v;
+}
+
 // conv_patch_gemm (3x3/s1/p1, W <= 64): fwd (plain or SCALED, optional
 // stats) and dgrad (TRANS, plain or ADDIN); in/out as in gather_gemm_launch.
-// The 64-channel 32-wide layer goes to conv_patch_ring instead.
+// The 64-channel 32-wide layer goes to conv_patch_ring instead, and the
+// layers of 128 channels and more at W = 4, 8 or 16 (whose 256-output tiles
+// start at the beginning of an image row) to conv_patch_stream; every other
+// width, ResNet-50's 56/28/14/7 among them, stays here.
 void patch_gemm_launch(bool trans, const at::Tensor& in,
                        const at::Tensor& wgt, const at::Tensor& bias,
                        const at::Tensor& addin, const float* asc,
@@ -2376,6 +2781,12 @@ void patch_gemm_launch(bool trans, const at::Tensor& in,
       Hi % 4 == 0 && !asc) {
     patch_ring_launch(trans, in, wgt, bias, addin, out, stats, b_row_stride,
                       b_rs_stride, act);
+    return;
+  }
+  if (patch_stream_on() && CI % 64 == 0 && CI >= 128 && KO % 64 == 0 &&
+      (Wi == 4 || Wi == 8 || Wi == 16) && !asc) {
+    patch_stream_launch(trans, in, wgt, bias, addin, out, stats, b_row_stride,
+                        b_rs_stride, act);
     return;
   }
   const long M = (long)N * Hi * Wi;
