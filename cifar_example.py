@@ -23,6 +23,12 @@ Env overrides (benchmark configs; CLI shape unchanged):
   MI355X_FP16=1 MI355X_DEVICE_SCALER=1      fp16 compute with
                                             amp.DeviceGradScaler: dynamic loss
                                             scaling, no host sync per step
+  MI355X_OPTIM=sgd|lars                     optimizer (default sgd); lars is
+                                            optim.LARS, for large batches
+  MI355X_LARS_ETA=<float>                   LARS trust coefficient (default
+                                            0.001)
+  MI355X_WD=<float>                         weight decay of either optimizer
+                                            (default 0)
 """
 
 import os
@@ -81,7 +87,13 @@ def main():
     net = build_model(os.environ.get("MI355X_MODEL", "net")).to(device)
     flat = FlatState(net)
     clip_norm = float(os.environ.get("MI355X_CLIP_NORM", "0")) or None
-    optimizer = optim.SGD(flat, lr=lr, momentum=0.9, max_grad_norm=clip_norm)
+    try:
+        optimizer = optim.from_env(flat, lr=lr, momentum=0.9,
+                                   max_grad_norm=clip_norm)
+    except ValueError as e:
+        raise SystemExit(str(e))
+    if "MI355X_OPTIM" in os.environ or "MI355X_WD" in os.environ:
+        print("optimizer:", optim.describe(optimizer))
     dev_scaler = None
     if os.environ.get("MI355X_DEVICE_SCALER", "0") == "1":
         if os.environ.get("MI355X_FP16", "0") != "1":

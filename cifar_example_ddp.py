@@ -25,7 +25,9 @@ MI355X_AUGMENT=1 (pad-4 random crop + flip on the train loader; needs
 MI355X_DEVICE_DATA), MI355X_CLIP_NORM=<float> (global-norm gradient
 clipping in the fused step; unset or 0 = off), MI355X_DEVICE_SCALER=1
 (with MI355X_FP16=1: amp.DeviceGradScaler, loss scaling without a host
-sync per step).
+sync per step), MI355X_OPTIM=sgd|lars (default sgd; lars is optim.LARS, for
+large batches), MI355X_LARS_ETA=<float> (LARS trust coefficient, default
+0.001), MI355X_WD=<float> (weight decay of either optimizer, default 0).
 """
 
 import argparse
@@ -123,8 +125,15 @@ def main(args):
     elif os.environ.get("MI355X_DEVICE_SCALER", "0") == "1":
         raise SystemExit("MI355X_DEVICE_SCALER=1 needs MI355X_FP16=1")
     clip_norm = float(os.environ.get("MI355X_CLIP_NORM", "0")) or None
-    optimizer = optim.SGD(net.flat, lr=lr, momentum=0.9,
-                          grad_scale=net.grad_scale, max_grad_norm=clip_norm)
+    try:
+        optimizer = optim.from_env(net.flat, lr=lr, momentum=0.9,
+                                   grad_scale=net.grad_scale,
+                                   max_grad_norm=clip_norm)
+    except ValueError as e:
+        raise SystemExit(str(e))
+    if args.rank == 0 and ("MI355X_OPTIM" in os.environ
+                           or "MI355X_WD" in os.environ):
+        print("optimizer:", optim.describe(optimizer))
 
     meter = None
     if os.environ.get("MI355X_LOG_SPEED", "0") == "1":

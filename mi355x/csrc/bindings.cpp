@@ -14,6 +14,14 @@ void sgd_step_guarded(at::Tensor p, at::Tensor g, at::Tensor m,
                       double gscale, double max_norm);
 void scaler_update(at::Tensor state, double gscale, double max_norm,
                    double growth, double backoff, long interval);
+void lars_stats(at::Tensor p, at::Tensor g, at::Tensor table, at::Tensor tens,
+                at::Tensor slab, at::Tensor state, at::Tensor stats,
+                double gscale, double max_norm, double wd, double eta,
+                double eps);
+void lars_step(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor table,
+               at::Tensor tens, at::Tensor state, at::Tensor stats,
+               c10::optional<at::Tensor> lr_dev, double lr, double mu,
+               double wd, double gscale, double max_norm);
 at::Tensor cast_to_16(at::Tensor src, at::Tensor like);
 at::Tensor cast_permute_krsc(at::Tensor w, at::Tensor like);
 at::Tensor cast_permute_krsc_pad(at::Tensor w, at::Tensor like);
@@ -85,6 +93,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("grad_stats", &grad_stats);
   m.def("sgd_step_guarded", &sgd_step_guarded);
   m.def("scaler_update", &scaler_update);
+  m.def("lars_stats", &lars_stats);
+  m.def("lars_step", &lars_step);
   m.def("cast_to_16", &cast_to_16);
   m.def("cast_permute_krsc", &cast_permute_krsc);
   m.def("cast_permute_krsc_pad", &cast_permute_krsc_pad);

@@ -36,31 +36,14 @@
 // Elementwise conventions as in elementwise.hip: 16 B/lane loads, grid-stride
 // loop, at most 2048 workgroups, scalar tail.
 #include "common.h"
+#include "guard.h"
 
 #include <climits>
 #include <cmath>
 
 namespace {
 
-enum GuardField {
-  kScale = 0,
-  kInvScale = 1,
-  kTracker = 2,
-  kSkipped = 3,
-  kNonFinite = 4,
-  kRawNorm = 5,
-  kLastNorm = 6,
-  kLastCoef = 7,
-  kStateLen = 8,
-};
-
 constexpr int kMaxBlocks = 2048;  // slab: [kMaxBlocks] sumsq + [kMaxBlocks] counts
-
-// inf or nan by the exponent field alone: a finite 3e38 stays finite here
-// although its square overflows
-DEV_INLINE int non_finite(float v) {
-  return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u;
-}
 
 __global__ __launch_bounds__(256) void grad_stats_kernel(
     const float* __restrict__ g, long n, float* __restrict__ slab_sq,
@@ -137,26 +120,6 @@ __global__ __launch_bounds__(256) void grad_stats_finalise_kernel(
   }
 }
 
-struct GuardCoef {
-  float norm, coef, eff;
-};
-
-// norm of the true (unscaled, world-averaged) gradient, the clip coefficient
-// and the multiplier the step applies. With no scaler (inv_scale == 1) and
-// max_norm == +inf, eff == gscale exactly.
-DEV_INLINE GuardCoef guard_coef(const float* st, float gscale,
-                                float max_norm) {
-  // every product rounded on its own: the step and the update kernel (and
-  // the CPU fallback) then agree on all three values to the bit
-#pragma clang fp contract(off)
-  GuardCoef r;
-  const float k = gscale * st[kInvScale];
-  r.norm = st[kRawNorm] * k;
-  r.coef = isinf(max_norm) ? 1.f : fminf(1.f, max_norm / (r.norm + 1e-6f));
-  r.eff = k * r.coef;
-  return r;
-}
-
 __global__ void sgd_guarded_kernel(float* __restrict__ p,
                                    const float* __restrict__ g,
                                    float* __restrict__ m, long n,
@@ -226,14 +189,6 @@ __global__ void scaler_update_kernel(float* st, float gscale, float max_norm,
 inline int gs_grid(long n) {
   long blocks = cdiv_l(n, (long)256 * 4);
   return (int)std::max<long>(1, std::min<long>(blocks, kMaxBlocks));
-}
-
-inline void check_f32(const at::Tensor& t, const char* name, long min_numel) {
-  TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
-  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
-  TORCH_CHECK(t.scalar_type() == at::kFloat, name, " must be float32");
-  TORCH_CHECK(t.numel() >= min_numel, name, " needs at least ", min_numel,
-              " elements");
 }
 
 }  // namespace

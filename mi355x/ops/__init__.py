@@ -7,6 +7,9 @@ from .functional import (  # noqa: F401
     gather_augment,
     global_avg_pool,
     grad_stats,
+    lars_plan,
+    lars_stats,
+    lars_step,
     linear,
     max_pool2d,
     scaler_update,

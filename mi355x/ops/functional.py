@@ -786,3 +786,159 @@ def scaler_update(state, grad_scale=1.0, max_norm=float("inf"),
     state[GS_INV_SCALE] = 1.0 / state[GS_SCALE]
     state[GS_LAST_NORM] = norm
     state[GS_LAST_COEF] = coef
+
+
+# ---------------------------------------------------------------------------
+# LARS: per-tensor norms and trust ratios over the flat buffers
+# ---------------------------------------------------------------------------
+
+LARS_TILE = 4096  # elements; kTile in mi355x/csrc/lars.hip
+LARS_MAX_TENSORS = 2048  # kMaxTensors there: the finalise block's LDS
+LARS_WNORM, LARS_GNORM, LARS_TRUST = 0, 1, 2  # columns of plan.stats
+
+
+class LarsPlan:
+    """What the LARS kernels need to know about the flat layout (layout of
+    the tables: mi355x/csrc/lars.hip). Built once by lars_plan.
+
+      table  int32 [T, 4]   tiles: {start, length, tensor, 0}
+      tens   int32 [S, 4]   tensors: {first tile, past last tile, excluded, 0}
+      slab   float32 [3*T]  pass 1's per-tile partials (GPU only)
+      stats  float32 [S, 3] per tensor: ||w_s||, raw ||g_s||, trust_s
+    """
+
+    def __init__(self, offsets, exclude, device):
+        offsets = [int(o) for o in offsets]
+        exclude = [bool(e) for e in exclude]
+        if len(offsets) < 2 or offsets[0] != 0:
+            raise ValueError("lars_plan: offsets must be S+1 ints from 0")
+        if any(b < a for a, b in zip(offsets, offsets[1:])):
+            raise ValueError("lars_plan: offsets must ascend")
+        if len(exclude) != len(offsets) - 1:
+            raise ValueError(f"lars_plan: {len(offsets) - 1} tensors but "
+                             f"{len(exclude)} exclude flags")
+        if len(exclude) > LARS_MAX_TENSORS:
+            raise ValueError(f"lars_plan: {len(exclude)} tensors, at most "
+                             f"{LARS_MAX_TENSORS} are supported")
+        if offsets[-1] >= 2 ** 31 - 1:
+            raise ValueError("lars_plan: 2^31 elements or more")
+        self.offsets, self.exclude = offsets, exclude
+        self.numel = offsets[-1]
+        self.device = torch.device(device)
+        tiles, tens = [], []
+        for s, (a, b) in enumerate(zip(offsets, offsets[1:])):
+            first = len(tiles)
+            tiles.extend((t, min(LARS_TILE, b - t), s, 0)
+                         for t in range(a, b, LARS_TILE))
+            tens.append((first, len(tiles), int(exclude[s]), 0))
+        S, T = len(tens), len(tiles)
+        self.table = torch.tensor(tiles, dtype=torch.int32).reshape(T, 4).to(
+            self.device)
+        self.tens = torch.tensor(tens, dtype=torch.int32).to(self.device)
+        self.slab = torch.empty(3 * T, dtype=torch.float32,
+                                device=self.device)
+        self.stats = torch.zeros(S, 3, dtype=torch.float32,
+                                 device=self.device)
+        self.stats[:, LARS_TRUST] = 1.0
+        # CPU fallback: per-element expansion of per-tensor values
+        self._sizes = torch.tensor([b - a for a, b in zip(offsets, offsets[1:])])
+        self._excluded = torch.tensor(exclude)
+
+    def check(self, *flats):
+        for f in flats:
+            if f.dim() != 1 or f.numel() != self.numel:
+                raise ValueError(
+                    f"LARS plan ends at element {self.numel} but the flat "
+                    f"buffer has shape {tuple(f.shape)}")
+
+    def per_element(self, per_tensor):
+        return torch.repeat_interleave(per_tensor, self._sizes)
+
+
+def lars_plan(offsets, exclude, device):
+    """Plan for lars_stats/lars_step: ``offsets`` are the S+1 ascending
+    element offsets of the S tensors in the flat buffers (0 first, numel
+    last), ``exclude`` S bools (True: trust 1 and no weight decay). Tensors
+    may start at any element and have any size; at most LARS_MAX_TENSORS
+    (2048) tensors and fewer than 2^31 elements."""
+    return LarsPlan(offsets, exclude, device)
+
+
+def lars_stats(flat_param, flat_grad, plan, state, grad_scale=1.0,
+               max_norm=float("inf"), weight_decay=0.0, eta=1e-3, eps=1e-8):
+    """One pass over ``flat_param`` and ``flat_grad``: the global raw norm
+    and inf/nan count of the gradient into ``state[4:6]`` (as grad_stats
+    leaves them) and, per tensor of the plan, into ``plan.stats``:
+
+        wn_s = ||w_s||,  raw ||g_s||,
+        trust_s = eta*wn_s / (gn_s + wd*wn_s + eps),  gn_s = ||g_s|| * eff
+                  (1 for an excluded tensor, or if wn_s or gn_s is 0)
+
+    with eff the guarded step's multiplier grad_scale*inv_scale*clip_coef.
+    GPU: per-tile partials, then one fixed-order combine in double: two
+    calls on the same buffers agree bit for bit. Returns plan.stats."""
+    max_norm = float(max_norm)
+    plan.check(flat_param, flat_grad)
+    if flat_param.is_cuda:
+        ext().lars_stats(flat_param, flat_grad, plan.table, plan.tens,
+                         plan.slab, state, plan.stats, grad_scale, max_norm,
+                         weight_decay, eta, eps)
+        return plan.stats
+    f32 = lambda v: torch.tensor(v, dtype=torch.float32)  # noqa: E731
+    S = len(plan.exclude)
+    sums = torch.zeros(S, 2, dtype=torch.float64)
+    for s, (a, b) in enumerate(zip(plan.offsets, plan.offsets[1:])):
+        sums[s, 0] = flat_param[a:b].double().square().sum()
+        sums[s, 1] = flat_grad[a:b].double().square().sum()
+    state.view(torch.int32)[GS_NONFINITE] = (
+        ~torch.isfinite(flat_grad)).sum().clamp(max=2**31 - 1)
+    state[GS_RAW_NORM] = sums[:, 1].sum().sqrt()
+    _, _, eff = _guard_coef(state, grad_scale, max_norm)
+    # float32, one rounding per op, in lars.hip's trust_ratio order
+    wn = sums[:, 0].sqrt().float()
+    gn_raw = sums[:, 1].sqrt().float()
+    gn = gn_raw * eff
+    den = (gn + f32(weight_decay) * wn) + f32(eps)
+    trust = (f32(eta) * wn) / den
+    keep = (wn > 0) & (gn > 0) & ~plan._excluded
+    plan.stats[:, LARS_WNORM] = wn
+    plan.stats[:, LARS_GNORM] = gn_raw
+    plan.stats[:, LARS_TRUST] = torch.where(keep, trust, torch.ones_like(trust))
+    return plan.stats
+
+
+def lars_step(flat_param, flat_grad, flat_momentum, plan, state, lr,
+              momentum, weight_decay=0.0, grad_scale=1.0,
+              max_norm=float("inf")):
+    """The LARS update with the trust ratios lars_stats left in the plan:
+
+        gr = g * eff + wd_s * w        (wd_s = 0 for an excluded tensor)
+        m  = mu * m + trust_s * gr
+        w -= lr * m
+
+    and nothing written at all if the gradient holds an inf/nan. ``lr`` is
+    a float or a 0-d float32 tensor on the buffers' device, read when the
+    kernel runs: a captured step then follows ``lr.fill_(v)``."""
+    max_norm = float(max_norm)
+    plan.check(flat_param, flat_grad, flat_momentum)
+    lr_t = lr if isinstance(lr, torch.Tensor) else None
+    if lr_t is not None and (lr_t.numel() != 1
+                             or lr_t.dtype != torch.float32
+                             or lr_t.device != flat_param.device):
+        raise ValueError("lars_step: a tensor lr must be one float32 element "
+                         "on the buffers' device")
+    if flat_param.is_cuda:
+        ext().lars_step(flat_param, flat_grad, flat_momentum, plan.table,
+                        plan.tens, state, plan.stats, lr_t,
+                        0.0 if lr_t is not None else lr, momentum,
+                        weight_decay, grad_scale, max_norm)
+        return
+    if int(state.view(torch.int32)[GS_NONFINITE]) != 0:
+        return
+    _, _, eff = _guard_coef(state, grad_scale, max_norm)
+    wd = torch.where(plan._excluded, 0.0, float(weight_decay)).float()
+    gr = flat_grad.mul(eff).add_(plan.per_element(wd) * flat_param)
+    gr.mul_(plan.per_element(plan.stats[:, LARS_TRUST]))
+    flat_momentum.mul_(momentum).add_(gr)
+    flat_param.sub_(flat_momentum * (lr_t.reshape(()) if lr_t is not None
+                                     else lr))

@@ -18,6 +18,7 @@ SRC = [
     "mi355x/csrc/bindings.cpp",
     "mi355x/csrc/elementwise.hip",
     "mi355x/csrc/gradstat.hip",
+    "mi355x/csrc/lars.hip",
     "mi355x/csrc/augment.hip",
     "mi355x/csrc/conv.hip",
     "mi355x/csrc/conv_mfma.hip",
