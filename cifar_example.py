@@ -29,6 +29,12 @@ Env overrides (benchmark configs; CLI shape unchanged):
                                             0.001)
   MI355X_WD=<float>                         weight decay of either optimizer
                                             (default 0)
+  MI355X_LABEL_SMOOTH=<float>               label smoothing of the training
+                                            loss (default 0)
+  MI355X_CUTMIX=<p> MI355X_MIXUP=<p>        probability that a train sample is
+                                            cutmixed / mixed up with its
+                                            partner in the batch (default 0;
+                                            need DEVICE_DATA, p's sum <= 1)
 """
 
 import os
@@ -61,6 +67,10 @@ def main():
     epochs = int(os.environ.get("MI355X_EPOCHS", "2"))
     lr = float(os.environ.get("MI355X_LR", "0.001"))
     max_steps = int(os.environ.get("MI355X_STEPS", "0"))  # 0 = full epochs
+    label_smooth = float(os.environ.get("MI355X_LABEL_SMOOTH", "0"))
+    cutmix = float(os.environ.get("MI355X_CUTMIX", "0"))
+    mixup = float(os.environ.get("MI355X_MIXUP", "0"))
+    soft_loss = label_smooth > 0 or cutmix + mixup > 0
 
     trainset, testset = get_datasets()
     # num_workers=2 mirrors the reference surface (cifar_example.py:47,52);
@@ -68,8 +78,15 @@ def main():
     if os.environ.get("MI355X_DEVICE_DATA", "0") == "1":
         # dataset resident on the device as uint8; one fused kernel per
         # batch builds it (gather + crop/flip + normalize + NHWC 16-bit)
-        augment = (Augment(pad=4, flip=True)
-                   if os.environ.get("MI355X_AUGMENT", "0") == "1" else None)
+        crop = os.environ.get("MI355X_AUGMENT", "0") == "1"
+        augment = None
+        if crop or cutmix + mixup > 0:
+            # cutmix/mixup alone mix uncropped, unflipped samples
+            try:
+                augment = Augment(pad=4 if crop else 0, flip=crop,
+                                  cutmix=cutmix, mixup=mixup)
+            except ValueError as e:
+                raise SystemExit(str(e))
         trainloader = DeviceLoader(trainset, batch_size=batch, shuffle=True,
                                    device=device, augment=augment)
         testloader = DeviceLoader(testset, batch_size=batch, shuffle=False,
@@ -77,6 +94,9 @@ def main():
     else:
         if os.environ.get("MI355X_AUGMENT", "0") == "1":
             raise SystemExit("MI355X_AUGMENT=1 needs MI355X_DEVICE_DATA=1")
+        for knob, p in (("MI355X_CUTMIX", cutmix), ("MI355X_MIXUP", mixup)):
+            if p > 0:
+                raise SystemExit(f"{knob}={p:g} needs MI355X_DEVICE_DATA=1")
         trainloader = DataLoader(trainset, batch_size=batch, shuffle=True,
                                  num_workers=2,
                                  device=device if device.type == "cuda" else None)
@@ -111,13 +131,16 @@ def main():
 
     t0 = time.time()
     steps = 0
+    loss_sum = 0.0
     for epoch in range(epochs):
         running_loss = 0.0
         for i, (inputs, labels) in enumerate(trainloader):
             inputs, labels = inputs.to(device), labels.to(device)
             optimizer.zero_grad()
             outputs = net(inputs)
-            loss = cross_entropy(outputs, labels)
+            # labels: a tensor, or a MixTarget under cutmix/mixup
+            loss = cross_entropy(outputs, labels,
+                                 label_smoothing=label_smooth)
             if dev_scaler is not None:
                 dev_scaler.scale(loss).backward()
                 optimizer.step(scaler=dev_scaler)
@@ -127,7 +150,9 @@ def main():
 
             if meter is not None:
                 meter.step(inputs.shape[0])
-            running_loss += loss.item()
+            step_loss = loss.item()
+            running_loss += step_loss
+            loss_sum += step_loss
             if i % 2000 == 1999:
                 print("[%d, %5d] loss: %.3f" %
                       (epoch + 1, i + 1, running_loss / 2000))
@@ -138,6 +163,10 @@ def main():
         if max_steps and steps >= max_steps:
             break
     print(f"Finished Training ({steps} steps, {time.time() - t0:.1f}s)")
+    if soft_loss:
+        print("soft-target loss: label_smoothing=%g cutmix=%g mixup=%g, "
+              "mean over the run %.4f" %
+              (label_smooth, cutmix, mixup, loss_sum / max(steps, 1)))
 
     PATH = os.environ.get("MI355X_CKPT", "./cifar_net.pth")
     torch.save(net.state_dict(), PATH)

@@ -77,11 +77,23 @@ std::vector<at::Tensor> cross_entropy_fwd(at::Tensor logits,
                                           at::Tensor target);
 at::Tensor cross_entropy_bwd(at::Tensor logits, at::Tensor target,
                              at::Tensor lse, at::Tensor dloss);
+std::vector<at::Tensor> cross_entropy_soft_fwd(
+    at::Tensor logits, at::Tensor y_a, c10::optional<at::Tensor> y_b,
+    c10::optional<at::Tensor> lam, double eps);
+at::Tensor cross_entropy_soft_bwd(at::Tensor logits, at::Tensor y_a,
+                                  c10::optional<at::Tensor> y_b,
+                                  c10::optional<at::Tensor> lam,
+                                  at::Tensor lse, at::Tensor dloss,
+                                  double eps);
 
 std::tuple<at::Tensor, at::Tensor> gather_augment(
     at::Tensor data_u8, at::Tensor targets, at::Tensor indices,
     at::Tensor scale, at::Tensor shift, int64_t pad, bool flip, int64_t seed,
     int64_t epoch, at::Tensor like);
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> gather_augment_mix(
+    at::Tensor data_u8, at::Tensor targets, at::Tensor indices,
+    at::Tensor scale, at::Tensor shift, int64_t pad, bool flip, int64_t tc,
+    int64_t tm, double inv_hw, int64_t seed, int64_t epoch, at::Tensor like);
 
 void register_rccl(py::module_& m);
 
@@ -119,5 +131,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_nt_mfma", &gemm_nt_mfma);
   m.def("cross_entropy_fwd", &cross_entropy_fwd);
   m.def("cross_entropy_bwd", &cross_entropy_bwd);
+  m.def("cross_entropy_soft_fwd", &cross_entropy_soft_fwd);
+  m.def("cross_entropy_soft_bwd", &cross_entropy_soft_bwd);
   m.def("gather_augment", &gather_augment);
+  m.def("gather_augment_mix", &gather_augment_mix);
 }

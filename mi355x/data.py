@@ -46,6 +46,10 @@ __all__ = [
     "DistributedSampler",
     "DataLoader",
     "augment_params",
+    "mix_params",
+    "MIX_NONE",
+    "MIX_CUT",
+    "MIX_UP",
     "Augment",
     "DeviceLoader",
 ]
@@ -442,18 +446,108 @@ def augment_params(seed: int, epoch: int, indices, pad: int, flip: bool):
     return tuple(torch.from_numpy(a.astype(np.int64)) for a in (dy, dx, f))
 
 
+MIX_NONE, MIX_CUT, MIX_UP = 0, 1, 2
+
+
+def _isqrt(n: np.ndarray) -> np.ndarray:
+    """Exact floor square root of non-negative int64 values below 2^62: a
+    double guess, off by at most one, then an integer correction."""
+    s = np.sqrt(n.astype(np.float64)).astype(np.int64)
+    s = s - (s * s > n)
+    s = s + ((s + 1) * (s + 1) <= n)
+    return s
+
+
+def mix_params(seed: int, epoch: int, indices, H: int, W: int,
+               cutmix: float, mixup: float):
+    """CutMix / Mixup draws of the samples ``indices`` in ``epoch``, for
+    H x W images: ``(mode, box, lam)``.
+
+      mode  int64 (B,)    MIX_NONE, MIX_CUT or MIX_UP
+      box   int64 (B,4)   cutmix rows [y0,y1) and columns [x0,x1), clipped
+                          to the image; zeros for the other modes
+      lam   float32 (B,)  weight of the sample's own image and label: 1 for
+                          none, u/65536 for mixup, kept area/(H*W) for cutmix
+
+    The draws continue augment_params' hash chain of the dataset index
+    (h, h2 -> h3, h4), so they too are the same at any batch size, world
+    size or rank; which sample is mixed IN is the loader's business (batch
+    position B-1-b). lam is uniform: Beta(1,1), the setting both papers use
+    on CIFAR; a general Beta(alpha) is not supported. This is the CPU twin
+    of mix_draw in csrc/augment.hip and the oracle of its tests.
+    """
+    from mi355x.ops.functional import mix_thresholds
+
+    tc, tm = mix_thresholds(cutmix, mixup)
+    H, W = int(H), int(W)
+    if not (1 <= H <= 1 << 23 and 1 <= W <= 1 << 23):
+        raise ValueError("mix_params: H and W must be in [1, 2^23]")
+    i = np.asarray(torch.as_tensor(indices, dtype=torch.int64).numpy())
+    if i.size and (i.min() < 0 or i.max() > 0xFFFFFFFF):
+        raise ValueError("mix_params: index outside uint32 range")
+    i = i.astype(np.uint64)
+    key0 = ((int(seed) & 0xFFFFFFFF) * _GOLDEN + (int(epoch) & 0xFFFFFFFF)) \
+        & 0xFFFFFFFF
+    key = _mix32(np.array(key0, dtype=np.uint64))
+    h = _mix32(i ^ key)
+    h2 = _mix32((h + np.uint64(_GOLDEN)) & _M32)
+    h3 = _mix32((h2 + np.uint64(_GOLDEN)) & _M32)
+    h4 = _mix32((h3 + np.uint64(_GOLDEN)) & _M32)
+    r = (h3 & np.uint64(0xFFFF)).astype(np.int64)
+    u = (h3 >> np.uint64(16)).astype(np.int64)
+    mode = np.where(r < tc, MIX_CUT, np.where(r < tc + tm, MIX_UP, MIX_NONE))
+    ch = _isqrt((H * H * (65536 - u)) >> 16)
+    cw = _isqrt((W * W * (65536 - u)) >> 16)
+    cy = ((h4 & np.uint64(0xFFFF)).astype(np.int64) * H) >> 16
+    cx = ((h4 >> np.uint64(16)).astype(np.int64) * W) >> 16
+    y0 = np.maximum(cy - ch // 2, 0)
+    y1 = np.minimum(cy - ch // 2 + ch, H)
+    x0 = np.maximum(cx - cw // 2, 0)
+    x1 = np.minimum(cx - cw // 2 + cw, W)
+    cut = mode == MIX_CUT
+    box = np.stack([y0, y1, x0, x1], axis=1) * cut[:, None]
+    keep = H * W - (y1 - y0) * (x1 - x0)
+    # one float32 multiply by the rounded reciprocal, as the kernel does
+    lam_cut = keep.astype(np.float32) * np.float32(1.0 / (H * W))
+    lam_up = u.astype(np.float32) * np.float32(1.0 / 65536.0)
+    lam = np.where(cut, lam_cut,
+                   np.where(mode == MIX_UP, lam_up, np.float32(1.0)))
+    return (torch.from_numpy(mode.astype(np.int64)),
+            torch.from_numpy(box.astype(np.int64)),
+            torch.from_numpy(lam.astype(np.float32)))
+
+
 class Augment:
     """Train-time augmentation settings: zero-pad by ``pad`` and take a
     random crop of the original size, then flip horizontally with
     probability 1/2 (the torchvision RandomCrop(padding=pad) +
-    RandomHorizontalFlip recipe). ``augment=None`` on a loader means none."""
+    RandomHorizontalFlip recipe). ``augment=None`` on a loader means none.
 
-    def __init__(self, pad: int = 4, flip: bool = True):
+    ``cutmix`` / ``mixup`` are the probabilities that a sample is mixed with
+    its partner in the batch (``ops.gather_augment_mix``); they must sum to
+    at most 1. With either above 0 a DeviceLoader yields ``(x, MixTarget)``
+    for ``ops.cross_entropy``; with both 0 nothing changes."""
+
+    def __init__(self, pad: int = 4, flip: bool = True, cutmix: float = 0.0,
+                 mixup: float = 0.0):
         self.pad = int(pad)
         self.flip = bool(flip)
+        self.cutmix = float(cutmix)
+        self.mixup = float(mixup)
+        if not (0.0 <= self.cutmix <= 1.0 and 0.0 <= self.mixup <= 1.0
+                and self.cutmix + self.mixup <= 1.0):
+            raise ValueError(
+                "cutmix and mixup must be probabilities with cutmix + mixup "
+                f"<= 1, got {self.cutmix} and {self.mixup}")
+
+    @property
+    def mixes(self) -> bool:
+        return self.cutmix + self.mixup > 0
 
     def __repr__(self) -> str:
-        return f"Augment(pad={self.pad}, flip={self.flip})"
+        mix = (f", cutmix={self.cutmix}, mixup={self.mixup}"
+               if self.mixes else "")
+        return f"Augment(pad={self.pad}, flip={self.flip}{mix})"
 
 
 class DeviceLoader:
@@ -475,6 +569,11 @@ class DeviceLoader:
     Yields ``(x, y)`` with x the NHWC buffer viewed as logical NCHW, so the
     models' ``to_model_layout`` permute back is contiguous already and
     copies nothing. ``device=None`` or a CPU device runs the CPU op (fp32).
+
+    With ``Augment(cutmix=..., mixup=...)`` above 0 the batch is built by
+    ``ops.gather_augment_mix`` instead (still one kernel) and the loader
+    yields ``(x, MixTarget(y_a, y_b, lam))``; the partner of batch position
+    b is position B-1-b of the same batch.
     """
 
     def __init__(self, dataset, batch_size: int = 1, shuffle: bool = False,
@@ -540,12 +639,23 @@ class DeviceLoader:
         idx_dev = idx.to(torch.int32).to(self.device)
         pad = self.augment.pad if self.augment is not None else 0
         flip = self.augment.flip if self.augment is not None else False
+        mixes = self.augment is not None and self.augment.mixes
         bs = self.batch_size
         total = idx.numel()
         for s in range(0, total, bs):
             e = min(s + bs, total)
             if self.drop_last and e - s < bs:
                 break
+            if mixes:
+                # the pair kernel in place of the plain one: still one
+                # launch per batch, and two labels plus a weight per row
+                x, y_a, y_b, lam = ops.gather_augment_mix(
+                    self.data_u8, self.targets, idx_dev[s:e], self.scale,
+                    self.shift, pad=pad, flip=flip,
+                    cutmix=self.augment.cutmix, mixup=self.augment.mixup,
+                    seed=self.seed, epoch=aug_epoch)
+                yield x.permute(0, 3, 1, 2), ops.MixTarget(y_a, y_b, lam)
+                continue
             x, y = ops.gather_augment(
                 self.data_u8, self.targets, idx_dev[s:e], self.scale,
                 self.shift, pad=pad, flip=flip, seed=self.seed,

@@ -15,6 +15,9 @@ extension (no silent PyTorch fallback on GPU).
 
 from __future__ import annotations
 
+from typing import NamedTuple
+
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -594,12 +597,83 @@ class _CEFn(torch.autograd.Function):
         return dlogits, None
 
 
-def cross_entropy(logits, target):
-    """Mean cross-entropy. logits [B,C] (16-bit on GPU), target int64 [B].
-    Reference call site: /root/reference/cifar_example.py:63,78."""
+class MixTarget(NamedTuple):
+    """Two labels per row and the weight of the first: what CutMix and
+    Mixup train against. ``y_a``, ``y_b`` int64 (B,), ``lam`` float32 (B,),
+    all on the logits' device. DeviceLoader yields one per batch when its
+    Augment mixes; cross_entropy takes it in place of a label tensor."""
+
+    y_a: torch.Tensor
+    y_b: torch.Tensor
+    lam: torch.Tensor
+
+    def to(self, *args, **kwargs):
+        return MixTarget(*(t.to(*args, **kwargs) for t in self))
+
+
+class _SoftCEFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, y_a, y_b, lam, eps):
+        loss, lse = ext().cross_entropy_soft_fwd(logits, y_a, y_b, lam, eps)
+        ctx.save_for_backward(logits, y_a, lse)
+        # y_b and lam may be None (a plain target): kept beside the saved
+        # tensors, they need no grad and are never written in place by us
+        ctx.rest = (y_b, lam, eps)
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        logits, y_a, lse = ctx.saved_tensors
+        y_b, lam, eps = ctx.rest
+        # dloss read on-device (hipGraph-capturable: no host sync)
+        if not (torch.is_tensor(dloss) and dloss.is_cuda):
+            dloss = torch.as_tensor(dloss, dtype=torch.float32,
+                                    device=logits.device)
+        dlogits = ext().cross_entropy_soft_bwd(
+            logits, y_a, y_b, lam, lse, dloss.float().reshape(()), eps)
+        return dlogits, None, None, None, None
+
+
+def cross_entropy(logits, target, label_smoothing=0.0):
+    """Mean cross-entropy. logits [B,C] (16-bit on GPU), target int64 [B]
+    or a MixTarget. Reference call site:
+    /root/reference/cifar_example.py:63,78.
+
+    With ``eps = label_smoothing`` the loss of a row is
+
+        lam*nll(y_a) + (1-lam)*nll(y_b),
+        nll(t) = (1-eps)*(lse - z_t) + eps*(lse - mean_c z_c)
+
+    (a plain target is y_a = y_b, lam = 1): F.cross_entropy(...,
+    label_smoothing=eps, reduction='none') mixed per row. GPU: one forward
+    and one backward kernel; both targets, lam and the upstream gradient
+    are read on the device, so a captured step follows new batches. A
+    target outside [0,C) in either slot makes the loss NaN. With
+    label_smoothing == 0 and a plain target this is the hard-label kernel
+    pair, unchanged."""
+    eps = float(label_smoothing)
+    if not 0.0 <= eps <= 1.0:
+        raise ValueError(f"label_smoothing must be in [0, 1], got {eps}")
+    mixed = isinstance(target, MixTarget)
     if logits.is_cuda:
-        return _CEFn.apply(logits, target)
-    return F.cross_entropy(logits.float(), target)
+        if not mixed and eps == 0.0:
+            return _CEFn.apply(logits, target)
+        if mixed:
+            return _SoftCEFn.apply(logits, target.y_a, target.y_b,
+                                   target.lam, eps)
+        return _SoftCEFn.apply(logits, target, None, None, eps)
+    if not mixed and eps == 0.0:
+        return F.cross_entropy(logits.float(), target)
+    lp = F.log_softmax(logits.float(), dim=1)
+    smooth = -lp.mean(dim=1)
+
+    def nll(t):
+        return (1.0 - eps) * -lp.gather(1, t[:, None])[:, 0] + eps * smooth
+
+    if not mixed:
+        return nll(target).mean()
+    lam = target.lam.float()
+    return (lam * nll(target.y_a) + (1.0 - lam) * nll(target.y_b)).mean()
 
 
 # ---------------------------------------------------------------------------
@@ -631,12 +705,20 @@ def gather_augment(data_u8, targets, indices, scale, shift, *, pad=0,
                                     int(pad), bool(flip), int(seed),
                                     int(epoch), like)
         return x, y
+    idx = indices.to(torch.int64)
+    v = _gather_raw_cpu(data_u8, idx, pad, flip, seed, epoch,
+                        "gather_augment")
+    return v * scale + shift, targets[idx]
+
+
+def _gather_raw_cpu(data_u8, idx, pad, flip, seed, epoch, who):
+    """The CPU ops' gather + crop + flip, before normalization: float32
+    (B,H,W,C) of raw byte values, a padded pixel 0."""
     from mi355x.data import augment_params
 
     N, H, W, _ = data_u8.shape
-    idx = indices.to(torch.int64)
     if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= N):
-        raise IndexError(f"gather_augment: index outside dataset of {N}")
+        raise IndexError(f"{who}: index outside dataset of {N}")
     dy, dx, f = augment_params(seed, epoch, idx, pad, flip)
     sh = torch.arange(H)[None, :] + (dy[:, None] - pad)             # (B,H)
     ww = torch.arange(W)[None, :]
@@ -644,8 +726,78 @@ def gather_augment(data_u8, targets, indices, scale, shift, *, pad=0,
     ok = ((sh >= 0) & (sh < H))[:, :, None] & ((sw >= 0) & (sw < W))[:, None, :]
     v = data_u8[idx[:, None, None], sh.clamp(0, H - 1)[:, :, None],
                 sw.clamp(0, W - 1)[:, None, :]]                     # (B,H,W,C)
-    v = v.to(torch.float32) * ok[..., None]
-    return v * scale + shift, targets[idx]
+    return v.to(torch.float32) * ok[..., None]
+
+
+def mix_thresholds(cutmix, mixup):
+    """The 16-bit mode thresholds (Tc, Tm) = round(p*65536) of the cutmix
+    and mixup probabilities; the kernel and the numpy twin both take them
+    from here."""
+    cutmix, mixup = float(cutmix), float(mixup)
+    if not (0.0 <= cutmix <= 1.0 and 0.0 <= mixup <= 1.0
+            and cutmix + mixup <= 1.0):
+        raise ValueError("cutmix and mixup must be probabilities with "
+                         f"cutmix + mixup <= 1, got {cutmix} and {mixup}")
+    tc, tm = int(round(cutmix * 65536)), int(round(mixup * 65536))
+    return tc, min(tm, 65536 - tc)
+
+
+def gather_augment_mix(data_u8, targets, indices, scale, shift, *, pad=0,
+                       flip=False, cutmix=0.0, mixup=0.0, seed=0, epoch=0):
+    """gather_augment with CutMix / Mixup: returns (x NHWC, y_a, y_b, lam).
+
+    Call A[b] what gather_augment builds for batch position b before it
+    normalizes (own crop and flip, padding raw 0). Position b's partner is
+    position B-1-b of the same call (the middle of an odd batch and B=1 pair
+    with themselves). Each position draws, from the hash of its own dataset
+    index (``mi355x.data.mix_params``), cutmix with probability ``cutmix``,
+    mixup with probability ``mixup``, else nothing:
+
+      none    x = A[b]                          lam = 1        y_b = y_a
+      cutmix  x = A[B-1-b] inside a box,        lam = kept     y_b = the
+              A[b] outside                      area / (H*W)   partner's
+      mixup   x = lam*A[b] + (1-lam)*A[B-1-b]   lam = u/65536  label
+
+    then ``v*scale[c] + shift[c]`` and one rounding, as gather_augment. lam
+    is uniform on [0,1): Beta(1,1), the CIFAR setting of both papers; a
+    general Beta(alpha) is not supported. The cutmix box has sides
+    sqrt(1-lam0)*(H,W) around a uniform centre and is clipped to the image;
+    lam is the area kept after the clip.
+
+    GPU: one kernel (one byte gather per none/cutmix element, two per mixup
+    element), x in the compute dtype, indices int32. CPU: fp32, bit-equal
+    before the rounding to 16 bits. Out-of-range indices: as
+    gather_augment (CPU raises IndexError; the kernel reads nothing for
+    them and gives label -1 in the slot concerned). No autograd.
+    """
+    tc, tm = mix_thresholds(cutmix, mixup)
+    N, H, W, _ = data_u8.shape
+    inv_hw = float(np.float32(1.0 / (H * W)))
+    if data_u8.is_cuda:
+        like = torch.empty(0, dtype=compute_dtype(), device=data_u8.device)
+        return tuple(ext().gather_augment_mix(
+            data_u8, targets, indices, scale, shift, int(pad), bool(flip),
+            tc, tm, inv_hw, int(seed), int(epoch), like))
+    from mi355x.data import MIX_CUT, MIX_NONE, MIX_UP, mix_params
+
+    idx = indices.to(torch.int64)
+    a = _gather_raw_cpu(data_u8, idx, pad, flip, seed, epoch,
+                        "gather_augment_mix")
+    p = a.flip(0)                                  # A[B-1-b]
+    mode, box, lam = mix_params(seed, epoch, idx, H, W, cutmix, mixup)
+    hh = torch.arange(H)[None, :, None]
+    ww = torch.arange(W)[None, None, :]
+    inbox = ((mode == MIX_CUT)[:, None, None]
+             & (hh >= box[:, 0, None, None]) & (hh < box[:, 1, None, None])
+             & (ww >= box[:, 2, None, None]) & (ww < box[:, 3, None, None]))
+    v = torch.where(inbox[..., None], p, a)
+    w = lam[:, None, None, None]
+    # fp32, and exact: see the kernel's comment
+    v = torch.where((mode == MIX_UP)[:, None, None, None],
+                    a * w + p * (1.0 - w), v)
+    y_a = targets[idx]
+    y_b = torch.where(mode == MIX_NONE, y_a, y_a.flip(0))
+    return v * scale + shift, y_a, y_b, lam
 
 
 # ---------------------------------------------------------------------------
