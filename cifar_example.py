@@ -35,6 +35,16 @@ Env overrides (benchmark configs; CLI shape unchanged):
                                             cutmixed / mixed up with its
                                             partner in the batch (default 0;
                                             need DEVICE_DATA, p's sum <= 1)
+  MI355X_SCHED=const|cosine|poly            learning-rate schedule over
+                                            epochs * len(train loader) steps,
+                                            peak MI355X_LR, advanced on the
+                                            device (default const)
+  MI355X_WARMUP_EPOCHS=<float>              linear warm-up from 0 in front of
+                                            cosine / poly (default 0)
+  MI355X_EMA=<decay>                        weight EMA in the fused step; a
+                                            second accuracy line and
+                                            <ckpt stem>_ema.pth (unset or 0 =
+                                            off)
 """
 
 import os
@@ -108,11 +118,14 @@ def main():
     flat = FlatState(net)
     clip_norm = float(os.environ.get("MI355X_CLIP_NORM", "0")) or None
     try:
-        optimizer = optim.from_env(flat, lr=lr, momentum=0.9,
-                                   max_grad_norm=clip_norm)
+        ema = optim.ema_from_env()
+        optimizer = optim.from_env(
+            flat, lr=optim.schedule_from_env(lr, len(trainloader), epochs),
+            momentum=0.9, max_grad_norm=clip_norm, ema=ema)
     except ValueError as e:
         raise SystemExit(str(e))
-    if "MI355X_OPTIM" in os.environ or "MI355X_WD" in os.environ:
+    if any(k in os.environ for k in ("MI355X_OPTIM", "MI355X_WD",
+                                     "MI355X_SCHED", "MI355X_EMA")):
         print("optimizer:", optim.describe(optimizer))
     dev_scaler = None
     if os.environ.get("MI355X_DEVICE_SCALER", "0") == "1":
@@ -171,21 +184,30 @@ def main():
     PATH = os.environ.get("MI355X_CKPT", "./cifar_net.pth")
     torch.save(net.state_dict(), PATH)
 
-    correct = 0
-    total = 0
-    net.eval()
-    with torch.no_grad():
-        for images, labels in testloader:
-            images, labels = images.to(device), labels.to(device)
-            outputs = net(images)
-            _, predicted = torch.max(outputs, 1)
-            total += labels.size(0)
-            correct += (predicted == labels).sum().item()
-            if max_steps and total >= max_steps * batch:
-                break
+    def evaluate():
+        correct = 0
+        total = 0
+        with torch.no_grad():
+            for images, labels in testloader:
+                images, labels = images.to(device), labels.to(device)
+                outputs = net(images)
+                _, predicted = torch.max(outputs, 1)
+                total += labels.size(0)
+                correct += (predicted == labels).sum().item()
+                if max_steps and total >= max_steps * batch:
+                    break
+        return 100 * correct / max(total, 1)
 
+    net.eval()
     print("Accuracy of the network on the 10000 test images: %d %%" %
-          (100 * correct / max(total, 1)))
+          evaluate())
+    if ema is not None:
+        # the averaged weights, with the live BN running statistics
+        with ema.swapped():
+            print("Accuracy of the EMA weights on the 10000 test images: "
+                  "%d %%" % evaluate())
+            stem, ext = os.path.splitext(PATH)
+            torch.save(net.state_dict(), stem + "_ema" + ext)
 
 
 if __name__ == "__main__":

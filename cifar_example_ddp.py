@@ -31,7 +31,13 @@ large batches), MI355X_LARS_ETA=<float> (LARS trust coefficient, default
 MI355X_LABEL_SMOOTH=<float> (label smoothing of the training loss, default
 0), MI355X_CUTMIX=<p> / MI355X_MIXUP=<p> (probability that a train sample
 is cutmixed / mixed up with its partner in the rank's batch, default 0;
-need MI355X_DEVICE_DATA, and the two sum to at most 1).
+need MI355X_DEVICE_DATA, and the two sum to at most 1),
+MI355X_SCHED=const|cosine|poly (learning-rate schedule over epochs *
+len(train loader) steps with peak MI355X_LR, advanced on the device; default
+const), MI355X_WARMUP_EPOCHS=<float> (linear warm-up from 0 in front of
+cosine / poly, default 0), MI355X_EMA=<decay> (weight EMA in the fused step:
+a second accuracy line, and rank 0 saves <ckpt stem>_ema.pth; unset or 0 =
+off).
 """
 
 import argparse
@@ -144,13 +150,16 @@ def main(args):
         raise SystemExit("MI355X_DEVICE_SCALER=1 needs MI355X_FP16=1")
     clip_norm = float(os.environ.get("MI355X_CLIP_NORM", "0")) or None
     try:
-        optimizer = optim.from_env(net.flat, lr=lr, momentum=0.9,
-                                   grad_scale=net.grad_scale,
-                                   max_grad_norm=clip_norm)
+        ema = optim.ema_from_env()
+        optimizer = optim.from_env(
+            net.flat,
+            lr=optim.schedule_from_env(lr, len(trainloader), epochs),
+            momentum=0.9, grad_scale=net.grad_scale, max_grad_norm=clip_norm,
+            ema=ema)
     except ValueError as e:
         raise SystemExit(str(e))
-    if args.rank == 0 and ("MI355X_OPTIM" in os.environ
-                           or "MI355X_WD" in os.environ):
+    if args.rank == 0 and any(k in os.environ for k in (
+            "MI355X_OPTIM", "MI355X_WD", "MI355X_SCHED", "MI355X_EMA")):
         print("optimizer:", optim.describe(optimizer))
 
     meter = None
@@ -212,21 +221,34 @@ def main(args):
     if args.rank == 0:  # rank-gated (fixes reference quirk 7); keys keep
         torch.save(net.state_dict(), PATH)  # the 'module.' prefix
 
-    accuracy = DistAccuracy(dist_sync_on_step=True, device=device)
+    def evaluate():
+        accuracy = DistAccuracy(dist_sync_on_step=True, device=device)
+        with torch.no_grad():
+            for n, (images, labels) in enumerate(testloader):
+                images, labels = images.to(device), labels.to(device)
+                outputs = net(images)
+                _, predicted = torch.max(outputs, 1)
+                accuracy.update(predicted, labels)
+                if max_steps and n >= max_steps:
+                    break
+        return accuracy.compute()
+
     net.eval()
-    with torch.no_grad():
-        for n, (images, labels) in enumerate(testloader):
-            images, labels = images.to(device), labels.to(device)
-            outputs = net(images)
-            _, predicted = torch.max(outputs, 1)
-            accuracy.update(predicted, labels)
-            if max_steps and n >= max_steps:
-                break
-    acc = accuracy.compute()
+    acc = evaluate()
     if args.rank == 0:
         # reference print format (/root/reference/cifar_example_ddp.py:135)
         print("Accuracy of the network on the 10000 test images: %d %%" %
               (100 * acc))
+    if ema is not None:
+        # the averaged weights, with the live BN running statistics; every
+        # rank holds the same average, rank 0 saves it
+        with ema.swapped():
+            acc = evaluate()
+            if args.rank == 0:
+                print("Accuracy of the EMA weights on the 10000 test "
+                      "images: %d %%" % (100 * acc))
+                stem, ext = os.path.splitext(PATH)
+                torch.save(net.state_dict(), stem + "_ema" + ext)
     comm.destroy()
 
 

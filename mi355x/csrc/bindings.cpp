@@ -10,8 +10,12 @@ void sgd_step(at::Tensor p, at::Tensor g, at::Tensor m, double lr, double mu,
               double wd, double gscale);
 void grad_stats(at::Tensor g, at::Tensor slab, at::Tensor out);
 void sgd_step_guarded(at::Tensor p, at::Tensor g, at::Tensor m,
-                      at::Tensor state, double lr, double mu, double wd,
-                      double gscale, double max_norm);
+                      at::Tensor state, c10::optional<at::Tensor> lr_dev,
+                      double lr, double mu, double wd, double gscale,
+                      double max_norm, c10::optional<at::Tensor> ema,
+                      c10::optional<at::Tensor> clock);
+void clock_advance(at::Tensor clock, c10::optional<at::Tensor> state,
+                   at::Tensor table, double decay, bool warmup);
 void scaler_update(at::Tensor state, double gscale, double max_norm,
                    double growth, double backoff, long interval);
 void lars_stats(at::Tensor p, at::Tensor g, at::Tensor table, at::Tensor tens,
@@ -21,7 +25,8 @@ void lars_stats(at::Tensor p, at::Tensor g, at::Tensor table, at::Tensor tens,
 void lars_step(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor table,
                at::Tensor tens, at::Tensor state, at::Tensor stats,
                c10::optional<at::Tensor> lr_dev, double lr, double mu,
-               double wd, double gscale, double max_norm);
+               double wd, double gscale, double max_norm,
+               c10::optional<at::Tensor> ema, c10::optional<at::Tensor> clock);
 at::Tensor cast_to_16(at::Tensor src, at::Tensor like);
 at::Tensor cast_permute_krsc(at::Tensor w, at::Tensor like);
 at::Tensor cast_permute_krsc_pad(at::Tensor w, at::Tensor like);
@@ -105,6 +110,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("grad_stats", &grad_stats);
   m.def("sgd_step_guarded", &sgd_step_guarded);
   m.def("scaler_update", &scaler_update);
+  m.def("clock_advance", &clock_advance);
   m.def("lars_stats", &lars_stats);
   m.def("lars_step", &lars_step);
   m.def("cast_to_16", &cast_to_16);

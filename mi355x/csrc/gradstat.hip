@@ -33,6 +33,26 @@
 // grad_stats writes its two results to any float32[2] {count, raw norm};
 // optim.SGD hands it state[4:6].
 //
+//   clock_advance     one thread, after scaler_update: counts the step if it
+//                     was applied and looks up what the next one uses
+//
+// Step clock: ONE float32[4] device tensor owned by the optimizer that has a
+// learning-rate schedule or a weight EMA. The update kernels read lr and the
+// EMA weight from it, so a captured step follows the schedule with no host
+// write, and a step skipped for overflow does not advance it.
+//
+//   [0] step      applied steps so far                     (int32)
+//   [1] lr        table[min(step, T-1)]: the lr the next
+//                 step uses                                 (float)
+//   [2] ema_omd   1 - d_step, the weight of the new
+//                 parameters in the next step's average     (float)
+//   [3] reserved  0
+//
+// d_t = decay, or min(decay, (1 + t) / (10 + t)) with the EMA warm-up, in
+// double and rounded once, so the host (which fills the clock for step 0
+// and after a checkpoint load) and the CPU fallback agree to the bit. The
+// schedule is a float32 table built on the host: no transcendental here.
+//
 // Elementwise conventions as in elementwise.hip: 16 B/lane loads, grid-stride
 // loop, at most 2048 workgroups, scalar tail.
 #include "common.h"
@@ -120,14 +140,24 @@ __global__ __launch_bounds__(256) void grad_stats_finalise_kernel(
   }
 }
 
+// lr by value, or read from the device (the clock's lr slot) when lr_dev is
+// given. kEma: the weight average e follows w in the same pass, with the
+// weight clock[kClkEmaOmd]; e and clock are not touched otherwise.
+template <bool kEma>
 __global__ void sgd_guarded_kernel(float* __restrict__ p,
                                    const float* __restrict__ g,
                                    float* __restrict__ m, long n,
-                                   const float* __restrict__ st, float lr,
-                                   float mu, float wd, float gscale_host,
-                                   float max_norm) {
+                                   const float* __restrict__ st,
+                                   const float* __restrict__ lr_dev,
+                                   float lr_host, float mu, float wd,
+                                   float gscale_host, float max_norm,
+                                   float* __restrict__ e,
+                                   const float* __restrict__ clock) {
   if (reinterpret_cast<const int*>(st)[kNonFinite] != 0) return;  // skipped: no write
   const float gscale = guard_coef(st, gscale_host, max_norm).eff;
+  const float lr = lr_dev ? *lr_dev : lr_host;
+  float omd = 0.f;
+  if constexpr (kEma) omd = clock[kClkEmaOmd];
   long i0 = (long)(blockIdx.x * blockDim.x + threadIdx.x) * 4;
   long stride = (long)gridDim.x * blockDim.x * 4;
   for (long i = i0; i < n; i += stride) {
@@ -135,22 +165,48 @@ __global__ void sgd_guarded_kernel(float* __restrict__ p,
       float4v vg = *reinterpret_cast<const float4v*>(g + i);
       float4v vp = *reinterpret_cast<const float4v*>(p + i);
       float4v vm = *reinterpret_cast<const float4v*>(m + i);
+      float4v ve;
+      if constexpr (kEma) ve = *reinterpret_cast<const float4v*>(e + i);
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         float gr = vg[k] * gscale + wd * vp[k];
         vm[k] = mu * vm[k] + gr;
         vp[k] -= lr * vm[k];
+        if constexpr (kEma) {
+          float a = ve[k];
+          ema_elem(a, vp[k], omd);
+          ve[k] = a;
+        }
       }
       *reinterpret_cast<float4v*>(m + i) = vm;
       *reinterpret_cast<float4v*>(p + i) = vp;
+      if constexpr (kEma) *reinterpret_cast<float4v*>(e + i) = ve;
     } else {
       for (long k = i; k < n; ++k) {
         float gr = g[k] * gscale + wd * p[k];
         m[k] = mu * m[k] + gr;
         p[k] -= lr * m[k];
+        if constexpr (kEma) ema_elem(e[k], p[k], omd);
       }
     }
   }
+}
+
+// One thread, launched after scaler_update on the same stream. st may be
+// null (no guard: every step counts). A skipped step leaves the clock alone.
+__global__ void clock_advance_kernel(float* ck, const float* st,
+                                     const float* __restrict__ table, int T,
+                                     double decay, int warmup) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  if (st && reinterpret_cast<const int*>(st)[kNonFinite] != 0) return;
+  int* cki = reinterpret_cast<int*>(ck);
+  const int prev = cki[kClkStep];
+  const int t = prev < INT_MAX ? max(prev, -1) + 1 : INT_MAX;
+  double d = decay;
+  if (warmup) d = fmin(decay, (1.0 + (double)t) / (10.0 + (double)t));
+  cki[kClkStep] = t;
+  ck[kClkLr] = table[min(t, T - 1)];
+  ck[kClkEmaOmd] = (float)(1.0 - d);
 }
 
 // One thread, launched after the guarded step on the same stream, so no SGD
@@ -208,8 +264,10 @@ void grad_stats(at::Tensor g, at::Tensor slab, at::Tensor out) {
 }
 
 void sgd_step_guarded(at::Tensor p, at::Tensor g, at::Tensor m,
-                      at::Tensor state, double lr, double mu, double wd,
-                      double gscale, double max_norm) {
+                      at::Tensor state, c10::optional<at::Tensor> lr_dev,
+                      double lr, double mu, double wd, double gscale,
+                      double max_norm, c10::optional<at::Tensor> ema,
+                      c10::optional<at::Tensor> clock) {
   check_f32(p, "p", 0);
   check_f32(g, "g", 0);
   check_f32(m, "m", 0);
@@ -217,11 +275,42 @@ void sgd_step_guarded(at::Tensor p, at::Tensor g, at::Tensor m,
   const long n = p.numel();
   TORCH_CHECK(g.numel() == n && m.numel() == n,
               "p, g and m must have the same number of elements");
-  hipLaunchKernelGGL(sgd_guarded_kernel, dim3(gs_grid(n)), dim3(256), 0,
-                     cur_stream(), p.data_ptr<float>(), g.data_ptr<float>(),
-                     m.data_ptr<float>(), n, state.data_ptr<float>(),
+  const float* lr_ptr = lr_dev.has_value() ? check_dev_scalar(*lr_dev, p)
+                                           : nullptr;
+  const dim3 grid(gs_grid(n)), block(256);
+  if (ema.has_value()) {
+    const EmaArgs a = check_ema(*ema, clock, p);
+    hipLaunchKernelGGL(sgd_guarded_kernel<true>, grid, block, 0, cur_stream(),
+                       p.data_ptr<float>(), g.data_ptr<float>(),
+                       m.data_ptr<float>(), n, state.data_ptr<float>(), lr_ptr,
+                       (float)lr, (float)mu, (float)wd, (float)gscale,
+                       (float)max_norm, a.e, a.clock);
+    return;
+  }
+  hipLaunchKernelGGL(sgd_guarded_kernel<false>, grid, block, 0, cur_stream(),
+                     p.data_ptr<float>(), g.data_ptr<float>(),
+                     m.data_ptr<float>(), n, state.data_ptr<float>(), lr_ptr,
                      (float)lr, (float)mu, (float)wd, (float)gscale,
-                     (float)max_norm);
+                     (float)max_norm, (float*)nullptr, (const float*)nullptr);
+}
+
+void clock_advance(at::Tensor clock, c10::optional<at::Tensor> state,
+                   at::Tensor table, double decay, bool warmup) {
+  check_f32(clock, "clock", kClkLen);
+  check_f32(table, "schedule table", 1);
+  TORCH_CHECK(table.numel() < (long)INT_MAX, "schedule table too long");
+  TORCH_CHECK(table.device() == clock.device(),
+              "the schedule table must live on the clock's device");
+  const float* st = nullptr;
+  if (state.has_value()) {
+    check_f32(*state, "state", kStateLen);
+    TORCH_CHECK(state->device() == clock.device(),
+                "the guard state must live on the clock's device");
+    st = state->data_ptr<float>();
+  }
+  hipLaunchKernelGGL(clock_advance_kernel, dim3(1), dim3(1), 0, cur_stream(),
+                     clock.data_ptr<float>(), st, table.data_ptr<float>(),
+                     (int)table.numel(), decay, (int)warmup);
 }
 
 void scaler_update(at::Tensor state, double gscale, double max_norm,

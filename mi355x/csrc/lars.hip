@@ -11,7 +11,9 @@
 //   lars_step    gr = g*eff + wd_s*w; m = mu*m + trust_s*gr; w -= lr*m,
 //                eff from the guard state (guard.h); writes nothing if the
 //                gradient holds an inf/nan. lr by value or read from a 0-d
-//                device tensor, so a captured step follows a schedule.
+//                device tensor, so a captured step follows a schedule. With
+//                an EMA buffer, e += omd*(w - e) in the same pass, omd from
+//                the step clock (gradstat.hip).
 //
 // The plan (built once on the host, mi355x.ops.lars_plan) cuts the flat
 // buffers into tiles of at most kTile elements that never cross a tensor
@@ -223,16 +225,22 @@ DEV_INLINE void lars_elem(float& w, float g, float& m, float eff, float wd,
   w = fmaf(-lr, m, w);
 }
 
+// kEma: the weight average e (w's layout and alignment) follows w in the
+// same pass with the weight clock[kClkEmaOmd]: head, body and tail as for w.
+// e and clock are not touched otherwise.
+template <bool kEma>
 __global__ __launch_bounds__(256) void lars_update_kernel(
     float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m,
     long n, const int4v* __restrict__ table, int T,
     const int4v* __restrict__ tens, int S, const float* __restrict__ st,
     const float* __restrict__ stats, const float* __restrict__ lr_dev,
     float lr_host, float mu, float wd_host, float gscale_host,
-    float max_norm) {
+    float max_norm, float* __restrict__ e, const float* __restrict__ clock) {
   if (reinterpret_cast<const int*>(st)[kNonFinite] != 0) return;  // skipped: no write
   const float eff = guard_coef(st, gscale_host, max_norm).eff;
   const float lr = lr_dev ? *lr_dev : lr_host;
+  float omd = 0.f;
+  if constexpr (kEma) omd = clock[kClkEmaOmd];
   const int tid = threadIdx.x;
   for (int t = blockIdx.x; t < T; t += gridDim.x) {
     const Tile q = load_tile(table, t, n, S);
@@ -242,12 +250,18 @@ __global__ __launch_bounds__(256) void lars_update_kernel(
     float* wt = w + q.start;
     const float* gt = g + q.start;
     float* mt = m + q.start;
-    if (tid < q.head)
+    float* et = nullptr;
+    if constexpr (kEma) et = e + q.start;
+    if (tid < q.head) {
       lars_elem(wt[tid], gt[tid], mt[tid], eff, wd, trust, mu, lr);
+      if constexpr (kEma) ema_elem(et[tid], wt[tid], omd);
+    }
     float4v* wv = reinterpret_cast<float4v*>(wt + q.head);
     const float4v* gv = reinterpret_cast<const float4v*>(gt + q.head);
     float4v* mv = reinterpret_cast<float4v*>(mt + q.head);
-    float4v vw[kVecs], vg[kVecs], vm[kVecs];
+    float4v* ev = nullptr;
+    if constexpr (kEma) ev = reinterpret_cast<float4v*>(et + q.head);
+    float4v vw[kVecs], vg[kVecs], vm[kVecs], ve[kVecs];
 #pragma unroll
     for (int k = 0; k < kVecs; ++k) {
       const int v = tid + k * 256;
@@ -255,6 +269,7 @@ __global__ __launch_bounds__(256) void lars_update_kernel(
         vg[k] = gv[v];
         vw[k] = wv[v];
         vm[k] = mv[v];
+        if constexpr (kEma) ve[k] = ev[v];
       }
     }
 #pragma unroll
@@ -267,14 +282,21 @@ __global__ __launch_bounds__(256) void lars_update_kernel(
           lars_elem(a, vg[k][j], b, eff, wd, trust, mu, lr);
           vw[k][j] = a;
           vm[k][j] = b;
+          if constexpr (kEma) {
+            float c = ve[k][j];
+            ema_elem(c, a, omd);
+            ve[k][j] = c;
+          }
         }
         mv[v] = vm[k];
         wv[v] = vw[k];
+        if constexpr (kEma) ev[v] = ve[k];
       }
     }
     if (tid < q.tail) {
       const int i = q.head + 4 * q.nvec + tid;
       lars_elem(wt[i], gt[i], mt[i], eff, wd, trust, mu, lr);
+      if constexpr (kEma) ema_elem(et[i], wt[i], omd);
     }
   }
 }
@@ -344,27 +366,31 @@ void lars_stats(at::Tensor p, at::Tensor g, at::Tensor table, at::Tensor tens,
 void lars_step(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor table,
                at::Tensor tens, at::Tensor state, at::Tensor stats,
                c10::optional<at::Tensor> lr_dev, double lr, double mu,
-               double wd, double gscale, double max_norm) {
+               double wd, double gscale, double max_norm,
+               c10::optional<at::Tensor> ema,
+               c10::optional<at::Tensor> clock) {
   const long n = p.numel();
   check_flat(p, "p", n);
   check_flat(g, "g", n);
   check_flat(m, "m", n);
   check_f32(state, "state", kStateLen);
   const PlanDims d = check_plan(table, tens, stats, n);
-  const float* lr_ptr = nullptr;
-  if (lr_dev.has_value()) {
-    check_f32(*lr_dev, "lr", 1);
-    TORCH_CHECK(lr_dev->numel() == 1, "a tensor lr must hold one element");
-    TORCH_CHECK(lr_dev->device() == p.device(),
-                "a tensor lr must live on the buffers' device");
-    lr_ptr = lr_dev->data_ptr<float>();
-  }
+  const float* lr_ptr = lr_dev.has_value() ? check_dev_scalar(*lr_dev, p)
+                                           : nullptr;
+  EmaArgs a = {nullptr, nullptr};
+  if (ema.has_value()) a = check_ema(*ema, clock, p);
   if (d.T == 0) return;
-  hipLaunchKernelGGL(
-      lars_update_kernel, dim3(d.grid), dim3(256), 0, cur_stream(),
-      p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), n,
-      reinterpret_cast<const int4v*>(table.data_ptr<int>()), d.T,
-      reinterpret_cast<const int4v*>(tens.data_ptr<int>()), d.S,
-      state.data_ptr<float>(), stats.data_ptr<float>(), lr_ptr, (float)lr,
-      (float)mu, (float)wd, (float)gscale, (float)max_norm);
+#define LARS_UPDATE(EMA)                                                     \
+  hipLaunchKernelGGL(                                                        \
+      lars_update_kernel<EMA>, dim3(d.grid), dim3(256), 0, cur_stream(),     \
+      p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), n,      \
+      reinterpret_cast<const int4v*>(table.data_ptr<int>()), d.T,            \
+      reinterpret_cast<const int4v*>(tens.data_ptr<int>()), d.S,             \
+      state.data_ptr<float>(), stats.data_ptr<float>(), lr_ptr, (float)lr,   \
+      (float)mu, (float)wd, (float)gscale, (float)max_norm, a.e, a.clock)
+  if (ema.has_value())
+    LARS_UPDATE(true);
+  else
+    LARS_UPDATE(false);
+#undef LARS_UPDATE
 }

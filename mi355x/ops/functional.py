@@ -882,9 +882,41 @@ def _guard_coef(state, grad_scale, max_norm):
     return norm, coef, k * coef
 
 
+def _lr_tensor(lr, flat_param, who):
+    """lr as the update kernels take it: None for a float, else the checked
+    one-element float32 tensor on the buffers' device."""
+    if not isinstance(lr, torch.Tensor):
+        return None
+    if (lr.numel() != 1 or lr.dtype != torch.float32
+            or lr.device != flat_param.device):
+        raise ValueError(f"{who}: a tensor lr must be one float32 element "
+                         "on the buffers' device")
+    return lr
+
+
+def _check_ema(ema, clock, flat_param, who):
+    if ema is None:
+        return
+    if clock is None:
+        raise ValueError(f"{who}: an EMA update needs the step clock")
+    if (ema.shape != flat_param.shape or ema.dtype != torch.float32
+            or ema.device != flat_param.device):
+        raise ValueError(f"{who}: ema must be float32 with the parameters' "
+                         "shape and device")
+    if (clock.numel() < CK_LEN or clock.dtype != torch.float32
+            or clock.device != flat_param.device):
+        raise ValueError(f"{who}: the clock must be float32[{CK_LEN}] on the "
+                         "buffers' device")
+
+
+def _ema_update_cpu(ema, flat_param, clock):
+    """e += omd * (w - e): the CPU form of csrc/guard.h's ema_elem."""
+    ema.add_(flat_param - ema, alpha=float(clock[CK_EMA_OMD]))
+
+
 def sgd_step_guarded(flat_param, flat_grad, flat_momentum, state, lr,
                      momentum, weight_decay=0.0, grad_scale=1.0,
-                     max_norm=float("inf")):
+                     max_norm=float("inf"), ema=None, clock=None):
     """sgd_step with the gradient multiplier taken from the guard ``state``
     that grad_stats filled (state[4:6]):
 
@@ -894,12 +926,21 @@ def sgd_step_guarded(flat_param, flat_grad, flat_momentum, state, lr,
 
     and nothing written at all if the gradient holds an inf/nan. No host
     sync on the GPU. With inv_scale == 1 and max_norm == inf this is
-    sgd_step bit for bit."""
+    sgd_step bit for bit.
+
+    ``lr`` is a float or a 0-d float32 tensor on the buffers' device (the
+    clock's CK_LR slot under a schedule), read when the kernel runs; the
+    arithmetic is the same either way. With ``ema`` (float32, the
+    parameters' layout) the same pass also does ``e += omd * (w_new - e)``,
+    omd = ``clock[CK_EMA_OMD]``; a skipped step leaves ``ema`` alone too."""
     max_norm = float(max_norm)
+    lr_t = _lr_tensor(lr, flat_param, "sgd_step_guarded")
+    _check_ema(ema, clock, flat_param, "sgd_step_guarded")
     if flat_param.is_cuda:
         ext().sgd_step_guarded(flat_param, flat_grad, flat_momentum, state,
-                               lr, momentum, weight_decay, grad_scale,
-                               max_norm)
+                               lr_t, 0.0 if lr_t is not None else lr,
+                               momentum, weight_decay, grad_scale, max_norm,
+                               ema, clock if ema is not None else None)
         return
     if int(state.view(torch.int32)[GS_NONFINITE]) != 0:
         return
@@ -908,7 +949,9 @@ def sgd_step_guarded(flat_param, flat_grad, flat_momentum, state, lr,
     if weight_decay != 0.0:
         g = g.add(flat_param, alpha=weight_decay)
     flat_momentum.mul_(momentum).add_(g)
-    flat_param.add_(flat_momentum, alpha=-lr)
+    flat_param.add_(flat_momentum, alpha=-float(lr))
+    if ema is not None:
+        _ema_update_cpu(ema, flat_param, clock)
 
 
 def scaler_update(state, grad_scale=1.0, max_norm=float("inf"),
@@ -938,6 +981,76 @@ def scaler_update(state, grad_scale=1.0, max_norm=float("inf"),
     state[GS_INV_SCALE] = 1.0 / state[GS_SCALE]
     state[GS_LAST_NORM] = norm
     state[GS_LAST_COEF] = coef
+
+
+# ---------------------------------------------------------------------------
+# step clock: learning-rate schedule and EMA weight, advanced on the device
+# ---------------------------------------------------------------------------
+
+# Step clock: one float32[4] tensor (layout: mi355x/csrc/gradstat.hip).
+# CK_STEP holds an int32 bit pattern: read it through clock.view(torch.int32).
+CK_STEP, CK_LR, CK_EMA_OMD = 0, 1, 2
+CK_LEN = 4
+
+
+def ema_one_minus_decay(step, ema_decay, ema_warmup):
+    """1 - d_t for applied-step number ``step``: d_t = ema_decay, or
+    min(ema_decay, (1 + t) / (10 + t)) with the warm-up. Computed in double
+    (a Python float); storing it into the float32 clock rounds it once, as
+    clock_advance_kernel does."""
+    d = float(ema_decay)
+    if ema_warmup:
+        d = min(d, (1.0 + step) / (10.0 + step))
+    return 1.0 - d
+
+
+def clock_set(clock, step, table, ema_decay=0.0, ema_warmup=False):
+    """Host write of the clock for ``step`` applied steps: what a new
+    optimizer (step 0) and a checkpoint load do. In place."""
+    step = int(step)
+    if not 0 <= step < 2 ** 31:
+        raise ValueError(f"clock_set: step {step} outside int32")
+    host = torch.zeros(CK_LEN, dtype=torch.float32)
+    host.view(torch.int32)[CK_STEP] = step
+    host[CK_LR] = table[min(step, table.numel() - 1)]
+    host[CK_EMA_OMD] = ema_one_minus_decay(step, ema_decay, ema_warmup)
+    clock.copy_(host)
+    return clock
+
+
+def new_clock(device, table, ema_decay=0.0, ema_warmup=False):
+    """A step clock at step 0 for the float32 schedule ``table``."""
+    return clock_set(torch.empty(CK_LEN, dtype=torch.float32, device=device),
+                     0, table, ema_decay, ema_warmup)
+
+
+def clock_advance(clock, state, table, ema_decay=0.0, ema_warmup=False):
+    """After scaler_update: count the step on the device and look up what
+    the next one uses. If ``state`` (a guard state, or None) reports a
+    non-finite gradient, nothing moves. Otherwise
+
+        t = ++clock[CK_STEP]
+        clock[CK_LR] = table[min(t, T-1)]
+        clock[CK_EMA_OMD] = 1 - d_t          (ema_one_minus_decay)
+
+    ``table`` is a float32 tensor of T >= 1 learning rates on the clock's
+    device. GPU: one thread, no host sync."""
+    if (table.dim() != 1 or table.numel() < 1 or table.dtype != torch.float32
+            or table.device != clock.device):
+        raise ValueError("clock_advance: the table must be a non-empty 1-D "
+                         "float32 tensor on the clock's device")
+    if clock.is_cuda:
+        ext().clock_advance(clock, state, table, float(ema_decay),
+                            bool(ema_warmup))
+        return
+    if (state is not None
+            and int(state.view(torch.int32)[GS_NONFINITE]) != 0):
+        return
+    ick = clock.view(torch.int32)
+    t = min(max(int(ick[CK_STEP]), -1) + 1, 2 ** 31 - 1)
+    ick[CK_STEP] = t
+    clock[CK_LR] = table[min(t, table.numel() - 1)]
+    clock[CK_EMA_OMD] = ema_one_minus_decay(t, ema_decay, ema_warmup)
 
 
 # ---------------------------------------------------------------------------
@@ -1061,7 +1174,7 @@ def lars_stats(flat_param, flat_grad, plan, state, grad_scale=1.0,
 
 def lars_step(flat_param, flat_grad, flat_momentum, plan, state, lr,
               momentum, weight_decay=0.0, grad_scale=1.0,
-              max_norm=float("inf")):
+              max_norm=float("inf"), ema=None, clock=None):
     """The LARS update with the trust ratios lars_stats left in the plan:
 
         gr = g * eff + wd_s * w        (wd_s = 0 for an excluded tensor)
@@ -1070,20 +1183,20 @@ def lars_step(flat_param, flat_grad, flat_momentum, plan, state, lr,
 
     and nothing written at all if the gradient holds an inf/nan. ``lr`` is
     a float or a 0-d float32 tensor on the buffers' device, read when the
-    kernel runs: a captured step then follows ``lr.fill_(v)``."""
+    kernel runs: a captured step then follows ``lr.fill_(v)`` or the step
+    clock's schedule. With ``ema`` (float32, the parameters' layout) the
+    same pass also does ``e += omd * (w_new - e)``, omd =
+    ``clock[CK_EMA_OMD]``; a skipped step leaves ``ema`` alone too."""
     max_norm = float(max_norm)
     plan.check(flat_param, flat_grad, flat_momentum)
-    lr_t = lr if isinstance(lr, torch.Tensor) else None
-    if lr_t is not None and (lr_t.numel() != 1
-                             or lr_t.dtype != torch.float32
-                             or lr_t.device != flat_param.device):
-        raise ValueError("lars_step: a tensor lr must be one float32 element "
-                         "on the buffers' device")
+    lr_t = _lr_tensor(lr, flat_param, "lars_step")
+    _check_ema(ema, clock, flat_param, "lars_step")
     if flat_param.is_cuda:
         ext().lars_step(flat_param, flat_grad, flat_momentum, plan.table,
                         plan.tens, state, plan.stats, lr_t,
                         0.0 if lr_t is not None else lr, momentum,
-                        weight_decay, grad_scale, max_norm)
+                        weight_decay, grad_scale, max_norm, ema,
+                        clock if ema is not None else None)
         return
     if int(state.view(torch.int32)[GS_NONFINITE]) != 0:
         return
@@ -1094,3 +1207,5 @@ def lars_step(flat_param, flat_grad, flat_momentum, plan, state, lr,
     flat_momentum.mul_(momentum).add_(gr)
     flat_param.sub_(flat_momentum * (lr_t.reshape(()) if lr_t is not None
                                      else lr))
+    if ema is not None:
+        _ema_update_cpu(ema, flat_param, clock)
