@@ -45,6 +45,13 @@ Env overrides (benchmark configs; CLI shape unchanged):
                                             second accuracy line and
                                             <ckpt stem>_ema.pth (unset or 0 =
                                             off)
+  MI355X_DEVICE_METER=1                     metrics.DeviceMeter: the training
+                                            loss is read from the device only
+                                            where a line is printed (no
+                                            loss.item() per step); evaluation
+                                            reads back once and also prints
+                                            test loss, top-5 and per-class
+                                            accuracy
 """
 
 import os
@@ -55,6 +62,7 @@ import torch
 from mi355x import optim
 from mi355x.data import (CIFAR10, Augment, DataLoader, DeviceLoader,
                          SyntheticImageDataset)
+from mi355x.metrics import DeviceMeter
 from mi355x.models import build_model
 from mi355x.ops import cross_entropy
 from mi355x.parallel.flat import FlatState
@@ -142,11 +150,20 @@ def main():
         from mi355x.utils import SpeedMeter
         meter = SpeedMeter(print_every=100)
 
+    # MI355X_DEVICE_METER=1: the loss window of the progress line and the
+    # whole-run total live on the device; nothing is read back per step
+    device_meter = os.environ.get("MI355X_DEVICE_METER", "0") == "1"
+    win_meter = run_meter = None
+
     t0 = time.time()
     steps = 0
     loss_sum = 0.0
     for epoch in range(epochs):
         running_loss = 0.0
+        if win_meter is not None:
+            # a new epoch starts a new window, as running_loss does
+            run_meter.merge(win_meter)
+            win_meter.reset()
         for i, (inputs, labels) in enumerate(trainloader):
             inputs, labels = inputs.to(device), labels.to(device)
             optimizer.zero_grad()
@@ -163,13 +180,26 @@ def main():
 
             if meter is not None:
                 meter.step(inputs.shape[0])
-            step_loss = loss.item()
-            running_loss += step_loss
-            loss_sum += step_loss
-            if i % 2000 == 1999:
-                print("[%d, %5d] loss: %.3f" %
-                      (epoch + 1, i + 1, running_loss / 2000))
-                running_loss = 0.0
+            if device_meter:
+                if win_meter is None:
+                    win_meter, run_meter = (
+                        DeviceMeter(outputs.shape[1], device=device)
+                        for _ in range(2))
+                win_meter.update(outputs, labels, loss=loss.detach())
+                if i % 2000 == 1999:
+                    print("[%d, %5d] loss: %.3f" %
+                          (epoch + 1, i + 1,
+                           win_meter.compute(sync=False)["loss"]))
+                    run_meter.merge(win_meter)
+                    win_meter.reset()
+            else:
+                step_loss = loss.item()
+                running_loss += step_loss
+                loss_sum += step_loss
+                if i % 2000 == 1999:
+                    print("[%d, %5d] loss: %.3f" %
+                          (epoch + 1, i + 1, running_loss / 2000))
+                    running_loss = 0.0
             steps += 1
             if max_steps and steps >= max_steps:
                 break
@@ -177,12 +207,45 @@ def main():
             break
     print(f"Finished Training ({steps} steps, {time.time() - t0:.1f}s)")
     if soft_loss:
+        if run_meter is not None:
+            # the one read of the run's total (row-weighted over the steps)
+            run_meter.merge(win_meter)
+            mean_loss = run_meter.compute(sync=False)["loss"]
+        else:
+            mean_loss = loss_sum / max(steps, 1)
         print("soft-target loss: label_smoothing=%g cutmix=%g mixup=%g, "
               "mean over the run %.4f" %
-              (label_smooth, cutmix, mixup, loss_sum / max(steps, 1)))
+              (label_smooth, cutmix, mixup, mean_loss))
 
     PATH = os.environ.get("MI355X_CKPT", "./cifar_net.pth")
     torch.save(net.state_dict(), PATH)
+
+    def evaluate_metered():
+        # one meter per evaluation, one read-back at its end
+        meter = None
+        total = 0
+        with torch.no_grad():
+            for images, labels in testloader:
+                images, labels = images.to(device), labels.to(device)
+                outputs = net(images)
+                if meter is None:
+                    meter = DeviceMeter(outputs.shape[1], topk=5,
+                                        confusion=True, device=device)
+                meter.update(outputs, labels)
+                total += labels.size(0)
+                if max_steps and total >= max_steps * batch:
+                    break
+        r = meter.compute()
+        # 100 * correct / total from the integer counts, as below
+        r["accuracy"] = 100 * round(r["top1"] * r["rows"]) / max(r["rows"], 1)
+        return r
+
+    def print_meter_lines(r):
+        print("Test loss: %.3f, top-5 accuracy: %.2f %%" %
+              (r["loss"], 100 * r["top5"]))
+        print("Per-class accuracy: " + " ".join(
+            "%d: %.1f %%" % (c, 100 * a)
+            for c, a in enumerate(r["per_class"].tolist())))
 
     def evaluate():
         correct = 0
@@ -199,13 +262,25 @@ def main():
         return 100 * correct / max(total, 1)
 
     net.eval()
-    print("Accuracy of the network on the 10000 test images: %d %%" %
-          evaluate())
+    if device_meter:
+        r = evaluate_metered()
+        print("Accuracy of the network on the 10000 test images: %d %%" %
+              r["accuracy"])
+        print_meter_lines(r)
+    else:
+        print("Accuracy of the network on the 10000 test images: %d %%" %
+              evaluate())
     if ema is not None:
         # the averaged weights, with the live BN running statistics
         with ema.swapped():
-            print("Accuracy of the EMA weights on the 10000 test images: "
-                  "%d %%" % evaluate())
+            if device_meter:
+                r = evaluate_metered()
+                print("Accuracy of the EMA weights on the 10000 test images: "
+                      "%d %%" % r["accuracy"])
+                print_meter_lines(r)
+            else:
+                print("Accuracy of the EMA weights on the 10000 test images: "
+                      "%d %%" % evaluate())
             stem, ext = os.path.splitext(PATH)
             torch.save(net.state_dict(), stem + "_ema" + ext)
 

@@ -37,7 +37,10 @@ len(train loader) steps with peak MI355X_LR, advanced on the device; default
 const), MI355X_WARMUP_EPOCHS=<float> (linear warm-up from 0 in front of
 cosine / poly, default 0), MI355X_EMA=<decay> (weight EMA in the fused step:
 a second accuracy line, and rank 0 saves <ckpt stem>_ema.pth; unset or 0 =
-off).
+off), MI355X_DEVICE_METER=1 (metrics.DeviceMeter: the training loss is read
+from the device only where a line is printed, with no loss.item() per step
+and no collective; an evaluation is one all-reduce and one read-back instead
+of one per batch, and also prints test loss, top-5 and per-class accuracy).
 """
 
 import argparse
@@ -49,7 +52,7 @@ import torch
 from mi355x import optim
 from mi355x.data import (CIFAR10, Augment, DataLoader, DeviceLoader,
                          DistributedSampler, SyntheticImageDataset)
-from mi355x.metrics import DistAccuracy
+from mi355x.metrics import DeviceMeter, DistAccuracy
 from mi355x.models import build_model
 from mi355x.ops import cross_entropy
 from mi355x.parallel import DistributedDataParallel, comm, sync_bn
@@ -167,12 +170,22 @@ def main(args):
         from mi355x.utils import SpeedMeter
         meter = SpeedMeter(print_every=100)
 
+    # MI355X_DEVICE_METER=1: the loss window of the progress line and the
+    # whole-run total live on the device; nothing is read back per step and
+    # the reads are local (rank 0 prints its own loss, as below)
+    device_meter = os.environ.get("MI355X_DEVICE_METER", "0") == "1"
+    win_meter = run_meter = None
+
     t0 = time.time()
     steps = 0
     loss_sum = 0.0
     for epoch in range(epochs):
         sampler_train.set_epoch(epoch)
         running_loss = 0.0
+        if win_meter is not None:
+            # a new epoch starts a new window, as running_loss does
+            run_meter.merge(win_meter)
+            win_meter.reset()
         for i, (inputs, labels) in enumerate(trainloader):
             inputs, labels = inputs.to(device), labels.to(device)
             optimizer.zero_grad()
@@ -198,13 +211,27 @@ def main(args):
 
             if meter is not None:
                 meter.step(inputs.shape[0])
-            step_loss = loss.item()
-            running_loss += step_loss
-            loss_sum += step_loss
-            if i % 2000 == 1999 and args.rank == 0:
-                print("[%d, %5d] loss: %.3f" %
-                      (epoch + 1, i + 1, running_loss / 2000))
-                running_loss = 0.0
+            if device_meter:
+                if win_meter is None:
+                    win_meter, run_meter = (
+                        DeviceMeter(outputs.shape[1], device=device)
+                        for _ in range(2))
+                win_meter.update(outputs, labels, loss=loss.detach())
+                if i % 2000 == 1999:
+                    if args.rank == 0:
+                        print("[%d, %5d] loss: %.3f" %
+                              (epoch + 1, i + 1,
+                               win_meter.compute(sync=False)["loss"]))
+                    run_meter.merge(win_meter)
+                    win_meter.reset()
+            else:
+                step_loss = loss.item()
+                running_loss += step_loss
+                loss_sum += step_loss
+                if i % 2000 == 1999 and args.rank == 0:
+                    print("[%d, %5d] loss: %.3f" %
+                          (epoch + 1, i + 1, running_loss / 2000))
+                    running_loss = 0.0
             steps += 1
             if max_steps and steps >= max_steps:
                 break
@@ -213,9 +240,15 @@ def main(args):
     if args.rank == 0:
         print(f"Finished Training ({steps} steps, {time.time() - t0:.1f}s)")
     if soft_loss and args.rank == 0:
+        if run_meter is not None:
+            # the one read of the run's total (row-weighted over the steps)
+            run_meter.merge(win_meter)
+            mean_loss = run_meter.compute(sync=False)["loss"]
+        else:
+            mean_loss = loss_sum / max(steps, 1)
         print("soft-target loss: label_smoothing=%g cutmix=%g mixup=%g, "
               "mean over the run %.4f" %
-              (label_smooth, cutmix, mixup, loss_sum / max(steps, 1)))
+              (label_smooth, cutmix, mixup, mean_loss))
 
     PATH = os.environ.get("MI355X_CKPT", "./cifar_net.pth")
     if args.rank == 0:  # rank-gated (fixes reference quirk 7); keys keep
@@ -233,20 +266,54 @@ def main(args):
                     break
         return accuracy.compute()
 
+    meter_result = {}
+
+    def evaluate_metered():
+        # one meter per evaluation: one all-reduce and one read-back at its
+        # end instead of one of each per batch
+        meter = None
+        with torch.no_grad():
+            for n, (images, labels) in enumerate(testloader):
+                images, labels = images.to(device), labels.to(device)
+                outputs = net(images)
+                if meter is None:
+                    meter = DeviceMeter(outputs.shape[1], topk=5,
+                                        confusion=True, device=device)
+                meter.update(outputs, labels)
+                if max_steps and n >= max_steps:
+                    break
+        meter_result.clear()
+        meter_result.update(meter.compute())
+        return meter_result["top1"]
+
+    def print_meter_lines():
+        r = meter_result
+        print("Test loss: %.3f, top-5 accuracy: %.2f %%" %
+              (r["loss"], 100 * r["top5"]))
+        print("Per-class accuracy: " + " ".join(
+            "%d: %.1f %%" % (c, 100 * a)
+            for c, a in enumerate(r["per_class"].tolist())))
+
+    run_eval = evaluate_metered if device_meter else evaluate
+
     net.eval()
-    acc = evaluate()
+    acc = run_eval()
     if args.rank == 0:
         # reference print format (/root/reference/cifar_example_ddp.py:135)
         print("Accuracy of the network on the 10000 test images: %d %%" %
               (100 * acc))
+        if device_meter:
+            print_meter_lines()
     if ema is not None:
         # the averaged weights, with the live BN running statistics; every
         # rank holds the same average, rank 0 saves it
         with ema.swapped():
-            acc = evaluate()
+            acc = run_eval()
             if args.rank == 0:
                 print("Accuracy of the EMA weights on the 10000 test "
                       "images: %d %%" % (100 * acc))
+                if device_meter:
+                    print_meter_lines()
                 stem, ext = os.path.splitext(PATH)
                 torch.save(net.state_dict(), stem + "_ema" + ext)
     comm.destroy()

@@ -90,6 +90,11 @@ at::Tensor cross_entropy_soft_bwd(at::Tensor logits, at::Tensor y_a,
                                   c10::optional<at::Tensor> lam,
                                   at::Tensor lse, at::Tensor dloss,
                                   double eps);
+void meter_update(at::Tensor state, at::Tensor slab, at::Tensor logits,
+                  at::Tensor y_a, c10::optional<at::Tensor> y_b,
+                  c10::optional<at::Tensor> lam, long k,
+                  c10::optional<at::Tensor> loss,
+                  c10::optional<at::Tensor> confusion, long pack);
 
 std::tuple<at::Tensor, at::Tensor> gather_augment(
     at::Tensor data_u8, at::Tensor targets, at::Tensor indices,
@@ -139,6 +144,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("cross_entropy_bwd", &cross_entropy_bwd);
   m.def("cross_entropy_soft_fwd", &cross_entropy_soft_fwd);
   m.def("cross_entropy_soft_bwd", &cross_entropy_soft_bwd);
+  m.def("meter_update", &meter_update);
   m.def("gather_augment", &gather_augment);
   m.def("gather_augment_mix", &gather_augment_mix);
 }

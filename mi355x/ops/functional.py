@@ -1209,3 +1209,115 @@ def lars_step(flat_param, flat_grad, flat_momentum, plan, state, lr,
                                      else lr))
     if ema is not None:
         _ema_update_cpu(ema, flat_param, clock)
+
+
+# ---------------------------------------------------------------------------
+# device-side meter: loss / top-k / confusion counts with no host read
+# ---------------------------------------------------------------------------
+
+# Meter state: one int64[8] tensor (layout: mi355x/csrc/meter.hip).
+# MT_LOSS_SUM holds a float64 bit pattern: read it through
+# state[MT_LOSS_SUM:MT_LOSS_SUM + 1].view(torch.float64).
+MT_ROWS, MT_CORRECT1, MT_CORRECTK, MT_BAD, MT_LOSS_SUM, MT_UPDATES = range(6)
+MT_LEN = 8
+METER_MAX_BLOCKS = 2048            # kMaxBlocks in meter.hip
+METER_SLAB = 4 * METER_MAX_BLOCKS  # int64: nll sums (float64 bits), 3 counts
+
+
+def _meter_nll_sum(nll, C):
+    """The sum of the rows' nll (float64 (B,), 0 for a bad row) in the order
+    meter.hip adds it for C columns: per row group over the grid's passes,
+    the block's groups in order, then meter_finalise_kernel's order."""
+    B = nll.numel()
+    rpb = 256 // (16 if C <= 16 else 64)          # rows per block pass
+    grid = max(1, min(-(-B // rpb), METER_MAX_BLOCKS))
+    per_pass = grid * rpb
+    passes = -(-B // per_pass)
+    x = F.pad(nll, (0, passes * per_pass - B)).reshape(passes, grid, rpb)
+    acc = x[0]
+    for p in range(1, passes):                     # a group's rows, in turn
+        acc = acc + x[p]
+    blk = acc[:, 0]
+    for j in range(1, rpb):                        # the block's groups
+        blk = blk + acc[:, j]
+    y = F.pad(blk, (0, METER_MAX_BLOCKS - grid)).reshape(-1, 256)
+    t = y[0]
+    for j in range(1, y.shape[0]):                 # thread t: t, t+256, ...
+        t = t + y[j]
+    w = t.reshape(4, 64)
+    lane = torch.arange(64, device=w.device)
+    for off in (32, 16, 8, 4, 2, 1):               # the xor butterfly
+        w = w + w[:, lane ^ off]
+    return (w[0, 0] + w[1, 0]) + (w[2, 0] + w[3, 0])
+
+
+def _meter_update_torch(state, logits, y_a, y_b, lam, k, loss, confusion):
+    """meter.hip's decisions in plain torch, on the logits' device, with no
+    host read."""
+    B, C = logits.shape
+    z = logits.detach().float()
+    t = y_a if y_b is None else torch.where(lam >= 0.5, y_a, y_b)
+    t_ok = (t >= 0) & (t < C)
+    ts = torch.where(t_ok, t, torch.zeros_like(t))  # never index with a bad one
+    zt = z.gather(1, ts[:, None])                   # (B,1)
+    mx = z.max(dim=1, keepdim=True).values
+    col = torch.arange(C, device=z.device)[None, :]
+    pred = torch.where(z == mx, col, C).min(dim=1).values
+    lse = (mx + (z - mx).exp().sum(dim=1, keepdim=True).log())[:, 0]
+    good = t_ok & torch.isfinite(lse)
+    rank = ((z > zt) | ((z == zt) & (col < ts[:, None]))).sum(dim=1)
+    nll = torch.where(good, (lse - zt[:, 0]).double(),
+                      torch.zeros((), dtype=torch.float64, device=z.device))
+    if loss is not None:
+        add = loss.detach().reshape(()).float().double() * float(B)
+    else:
+        add = _meter_nll_sum(nll, C)
+    state[MT_ROWS] += B
+    state[MT_CORRECT1] += (good & (rank == 0)).sum()
+    state[MT_CORRECTK] += (good & (rank < k)).sum()
+    state[MT_BAD] += (~good).sum()
+    state[MT_LOSS_SUM:MT_LOSS_SUM + 1].view(torch.float64).add_(add)
+    state[MT_UPDATES] += 1
+    if confusion is not None:
+        cell = torch.where(good, ts * C + pred.clamp(max=C - 1),
+                           torch.zeros_like(ts))
+        confusion.view(-1).index_add_(0, cell, good.to(torch.int64))
+
+
+def meter_update(state, slab, logits, y_a, y_b=None, lam=None, *, k,
+                 loss=None, confusion=None):
+    """Add one batch to a meter ``state`` (int64[MT_LEN], layout in
+    mi355x/csrc/meter.hip), on the logits' device and with no host read.
+
+    logits (B,C); the row's label is ``y_a``, or with a mix target
+    ``lam >= 0.5 ? y_a : y_b``. Per row: lse and nll = lse - z_t (fp32, the
+    hard-label loss kernel's arithmetic), pred = the first index of the row
+    maximum, rank = #{c : z_c > z_t} + #{c < t : z_c == z_t}. A row is bad
+    if its label lies outside [0,C) or its lse is not finite; it counts in
+    rows and bad and nowhere else. A good row is correct@1 if rank == 0,
+    correct@k if rank < k, adds its nll to the loss sum and one to
+    ``confusion[t, pred]`` (int64 (C,C), optional). With ``loss`` (0-d
+    float32 on the device, the batch's mean loss as the training loop has
+    it) the loss sum takes ``double(loss) * B`` instead of the rows' nll.
+
+    16-bit logits on the GPU: two kernels, per-block partials in ``slab``
+    (int64[METER_SLAB]) combined in one fixed order, so two runs agree bit
+    for bit. CPU tensors, and GPU logits that are not 16-bit, run plain
+    torch ops that make the same decisions: counts and matrix equal the
+    kernel's, and so does the loss sum under ``loss=``."""
+    k = int(k)
+    if k < 1:
+        raise ValueError(f"meter_update: k must be at least 1, got {k}")
+    if logits.dim() != 2 or logits.shape[0] < 1 or logits.shape[1] < 1:
+        raise ValueError("meter_update: logits must be (B,C) with B, C >= 1")
+    if (y_b is None) != (lam is None):
+        raise ValueError("meter_update: y_b and lam come together")
+    if logits.is_cuda and logits.dtype in (torch.bfloat16, torch.float16):
+        if loss is not None:
+            loss = loss.detach().reshape(())
+            if loss.dtype != torch.float32:
+                loss = loss.float()
+        ext().meter_update(state, slab, logits.detach(), y_a, y_b, lam, k,
+                           loss, confusion, 0)
+        return
+    _meter_update_torch(state, logits, y_a, y_b, lam, k, loss, confusion)

@@ -30,6 +30,7 @@ SRC = [
     "mi355x/csrc/gemm_mfma.hip",
     "mi355x/csrc/stem_mfma.hip",
     "mi355x/csrc/loss.hip",
+    "mi355x/csrc/meter.hip",
     "mi355x/csrc/rccl_comm.cpp",
 ]
 
