@@ -8,7 +8,9 @@ print. Differences are conscious fixes of reference bugs:
 no dead `dataiter.next()` (removed API), no dead imshow/matplotlib.
 
 Env overrides (benchmark configs; CLI shape unchanged):
-  MI355X_MODEL=net|resnet18|resnet50        (default net)
+  MI355X_MODEL=net|resnet18|resnet50|mobilenet  (default net; mobilenet
+                                            is CPU-only: no depthwise GPU
+                                            kernel yet)
   MI355X_SYNTHETIC=1                        synthetic 32x32 data (no download)
   MI355X_BATCH / MI355X_EPOCHS / MI355X_STEPS / MI355X_LR
   MI355X_DEVICE=cpu|cuda                    (default cpu, like the reference)

@@ -16,7 +16,8 @@ comm.init_process_group builds a 1-rank group).
 Launch:  python -m mi355x.launcher --nproc-per-node 8 cifar_example_ddp.py
    (or)  torchrun --nproc-per-node 8 cifar_example_ddp.py
 
-Env overrides (benchmark configs; CLI shape unchanged): MI355X_MODEL,
+Env overrides (benchmark configs; CLI shape unchanged): MI355X_MODEL
+(net, resnet18, resnet50, or mobilenet, which is CPU-only for now),
 MI355X_SYNTHETIC, MI355X_BATCH, MI355X_EPOCHS, MI355X_STEPS, MI355X_LR,
 MI355X_SYNC_BN=1, MI355X_FP16=1 (fp16 compute + dynamic loss scaling),
 MI355X_CKPT (checkpoint path, default ./cifar_net.pth),

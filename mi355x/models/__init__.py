@@ -1,3 +1,4 @@
+from .mobilenet import MobileNet, mobilenet  # noqa: F401
 from .net import Net  # noqa: F401
 from .resnet import ResNet, resnet18, resnet50  # noqa: F401
 
@@ -14,4 +15,6 @@ def build_model(name: str, num_classes: int = 10):
         return resnet50(num_classes=num_classes, stem="imagenet")
     if name == "resnet50_cifar":
         return resnet50(num_classes=num_classes, stem="cifar")
+    if name == "mobilenet":
+        return mobilenet(num_classes=num_classes)
     raise ValueError(f"unknown model {name!r}")

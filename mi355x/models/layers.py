@@ -25,12 +25,21 @@ def to_model_layout(x: torch.Tensor) -> torch.Tensor:
 
 
 class Conv2d(nn.Module):
+    """groups: 1, or in_channels for a depthwise convolution (ops.conv2d
+    lists what it supports). The weight has torch's shape
+    [out_channels, in_channels // groups, k, k]."""
+
     def __init__(self, in_channels, out_channels, kernel_size, stride=1,
-                 padding=0, bias=True, act=None):
+                 padding=0, bias=True, act=None, groups=1):
         super().__init__()
+        if groups < 1 or in_channels % groups or out_channels % groups:
+            raise ValueError(f"Conv2d: groups={groups} does not divide "
+                             f"{in_channels} and {out_channels} channels")
         self.stride, self.padding, self.act = stride, padding, act
+        self.groups = groups
         self.weight = nn.Parameter(
-            torch.empty(out_channels, in_channels, kernel_size, kernel_size))
+            torch.empty(out_channels, in_channels // groups, kernel_size,
+                        kernel_size))
         self.bias = nn.Parameter(torch.empty(out_channels)) if bias else None
         self.reset_parameters()
 
@@ -43,7 +52,7 @@ class Conv2d(nn.Module):
 
     def forward(self, x):
         return ops.conv2d(x, self.weight, self.bias, self.stride,
-                          self.padding, self.act)
+                          self.padding, self.act, self.groups)
 
 
 class Linear(nn.Module):

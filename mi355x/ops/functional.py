@@ -364,13 +364,57 @@ def conv2d_with_stats(x, weight, stride=1, padding=0):
     return _ConvFn.apply(x, weight, None, stride, padding, _ACT_NONE, True)
 
 
-def conv2d(x, weight, bias=None, stride=1, padding=0, act=None):
-    """2-D convolution. x: NHWC; weight: fp32 [K,C,R,S] (torch layout).
+def _check_depthwise(x, weight, stride, padding, groups):
+    """The depthwise domain: every value outside it is named in a
+    ValueError."""
+    C = x.shape[-1]
+    if groups != C:
+        raise ValueError(
+            f"conv2d: groups={groups} is not supported: only groups=1 and "
+            f"groups == channels ({C}), the depthwise case")
+    if weight.shape[0] != groups or weight.shape[1] != 1:
+        raise ValueError(
+            f"conv2d: a depthwise weight must be [{groups}, 1, R, R] "
+            f"(channel multiplier 1), got {tuple(weight.shape)}")
+    R, S = weight.shape[2], weight.shape[3]
+    if R != S or R not in (3, 5):
+        raise ValueError(
+            f"conv2d: depthwise kernels are 3x3 or 5x5, got {R}x{S}")
+    if stride not in (1, 2):
+        raise ValueError(
+            f"conv2d: depthwise stride must be 1 or 2, got {stride!r}")
+    if not isinstance(padding, int) or not 0 <= padding <= R - 1:
+        raise ValueError(
+            f"conv2d: depthwise padding must be in [0, {R - 1}] for a "
+            f"{R}x{R} kernel, got {padding!r}")
+
+
+def conv2d(x, weight, bias=None, stride=1, padding=0, act=None, groups=1):
+    """2-D convolution. x: NHWC; weight: fp32 [K,C/groups,R,S] (torch
+    layout).
 
     act: None | 'relu' fused into the epilogue (and into the kernel backward
     mask). Reference call sites: /root/reference/cifar_example.py:20-29.
+
+    groups: 1 (dense), or the channel count of x (depthwise: weight
+    [C,1,R,R] with R in {3,5}, stride 1 or 2, padding <= R-1). Anything
+    else raises ValueError. The depthwise case runs on the CPU path only:
+    the kernel library has no depthwise kernel, so on the GPU it raises
+    NotImplementedError (never an eager-torch fallback). A depthwise weight
+    never reaches _w16_conv.
     """
     a = _ACT_RELU if act == "relu" else _ACT_NONE
+    if groups != 1:
+        _check_depthwise(x, weight, stride, padding, groups)
+        if x.is_cuda:
+            raise NotImplementedError(
+                "conv2d: depthwise convolution (groups == channels) has no "
+                "GPU kernel in this library yet; it runs on the CPU path "
+                "only")
+        y = F.conv2d(x.permute(0, 3, 1, 2), weight, bias, stride, padding,
+                     groups=groups)
+        y = y.permute(0, 2, 3, 1)
+        return F.relu(y) if a == _ACT_RELU else y
     if x.is_cuda:
         return _ConvFn.apply(x, weight, bias, stride, padding, a)
     y = F.conv2d(x.permute(0, 3, 1, 2), weight, bias, stride, padding)
