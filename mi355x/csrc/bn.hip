@@ -331,7 +331,10 @@ __global__ void bn_finalize_kernel(const float* __restrict__ stats,  // [2,C]
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
   const float mean = stats[c] * inv_m;
-  const float var = stats[C + c] * inv_m - mean * mean;
+  // sumsq/M - mean^2 cancels: for a channel with |mean| >> std its fp32
+  // error exceeds eps, and an unclamped negative value would make invstd
+  // NaN and running_var negative. relu_f keeps a NaN from the stats.
+  const float var = relu_f(stats[C + c] * inv_m - mean * mean);
   out[c] = mean;
   out[C + c] = rsqrtf(var + eps);
   if (rmean) {

@@ -12,6 +12,16 @@
 
 namespace {
 
+// Does tap value f replace the running maximum? The first in-image tap
+// always does (no sentinel: an all -inf window gives -inf, and idx always
+// names an in-image tap); after it a larger value does, the first of equal
+// values stays, and a NaN wins and then sticks (!(f <= best) is true for a
+// NaN f, best == best false for a NaN best), as in torch.max_pool2d: a
+// forward NaN has to reach the gradient, where the loss scaler looks.
+DEV_INLINE bool pool_takes(bool first, float f, float best) {
+  return first || (!(f <= best) && best == best);
+}
+
 // C%8 fast path: one thread owns 8 channels of one output; window taps
 // are short8 loads (16B), argmax kept per sub-lane, indices stored as one
 // 8-byte pack. 8x fewer memory instructions than the scalar variant
@@ -31,13 +41,9 @@ __global__ void maxpool_fwd_vec8(const T16* __restrict__ x,
     long np = npq / Q;
     const int p = (int)(np % P);
     const int n = (int)(np / P);
-    float best[8];
-    int rs[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      best[u] = -3.4e38f;
-      rs[u] = 0;
-    }
+    float best[8] = {};
+    int rs[8] = {};
+    bool first = true;  // no in-image tap seen yet (pad <= k/2: there is one)
     for (int r = 0; r < kh; ++r) {
       const int ih = p * stride - pad + r;
       if (ih < 0 || ih >= H) continue;
@@ -49,11 +55,12 @@ __global__ void maxpool_fwd_vec8(const T16* __restrict__ x,
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
           const float f = s16_to_f32<T16>(v[u]);
-          if (f > best[u]) {
+          if (pool_takes(first, f, best[u])) {
             best[u] = f;
             rs[u] = r * kw + sx;
           }
         }
+        first = false;
       }
     }
     short8 yv;
@@ -87,8 +94,9 @@ __global__ void maxpool_fwd_kernel(const T16* __restrict__ x,
     long np = npq / Q;
     const int p = (int)(np % P);
     const int n = (int)(np / P);
-    float best = -3.4e38f;
+    float best = 0.f;
     int best_rs = 0;
+    bool first = true;
     for (int r = 0; r < kh; ++r) {
       const int ih = p * stride - pad + r;
       if (ih < 0 || ih >= H) continue;
@@ -97,10 +105,11 @@ __global__ void maxpool_fwd_kernel(const T16* __restrict__ x,
         if (iw < 0 || iw >= W) continue;
         const float v =
             F16<T16>::to_f32(x[(((long)n * H + ih) * W + iw) * C + c]);
-        if (v > best) {
+        if (pool_takes(first, v, best)) {
           best = v;
           best_rs = r * kw + s;
         }
+        first = false;
       }
     }
     y[t] = F16<T16>::from_f32(best);
@@ -223,6 +232,10 @@ std::vector<at::Tensor> maxpool_fwd(at::Tensor x, long kernel, long stride,
   // relative argmax is one byte (r*kw+s) — larger windows would alias
   TORCH_CHECK(kernel * kernel <= 256, "maxpool window ", kernel, "x", kernel,
               " exceeds the byte-packed argmax range (kernel^2 must be <=256)");
+  // a window must hold an in-image tap (torch's rule too): with more
+  // padding the output would be a maximum over nothing
+  TORCH_CHECK(pad >= 0 && pad <= kernel / 2, "maxpool pad ", pad,
+              " must be at most half the kernel size ", kernel);
   const int N = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3);
   const int P = (H + 2 * pad - kernel) / stride + 1;
   const int Q = (W + 2 * pad - kernel) / stride + 1;
@@ -253,6 +266,10 @@ at::Tensor maxpool_bwd(at::Tensor dy, at::Tensor idx, long H, long W,
   CHECK_CONTIG(dy);
   TORCH_CHECK(kernel * kernel <= 256, "maxpool window ", kernel, "x", kernel,
               " exceeds the byte-packed argmax range (kernel^2 must be <=256)");
+  // a window must hold an in-image tap (torch's rule too): with more
+  // padding the output would be a maximum over nothing
+  TORCH_CHECK(pad >= 0 && pad <= kernel / 2, "maxpool pad ", pad,
+              " must be at most half the kernel size ", kernel);
   const int N = dy.size(0), P = dy.size(1), Q = dy.size(2), C = dy.size(3);
   auto dx = at::empty({N, H, W, (long)C}, dy.options());
   DISPATCH_16(dy, T16, {

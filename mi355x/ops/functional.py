@@ -589,7 +589,11 @@ class _MaxPoolFn(torch.autograd.Function):
 
 
 def max_pool2d(x, kernel, stride=None, padding=0):
-    """Max pooling over NHWC. Reference: /root/reference/cifar_example.py:21."""
+    """Max pooling over NHWC. Reference: /root/reference/cifar_example.py:21.
+
+    torch.max_pool2d's rules: padding <= kernel // 2 (else an error),
+    padding never wins, a NaN in a window gives NaN, and the gradient goes
+    to the first maximum in scan order."""
     stride = stride or kernel
     if x.is_cuda:
         return _MaxPoolFn.apply(x, kernel, stride, padding)
