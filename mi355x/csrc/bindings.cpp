@@ -66,6 +66,15 @@ std::vector<at::Tensor> bn_bwd_dx(at::Tensor x, at::Tensor dy, at::Tensor y,
                                   bool want_dres, at::Tensor mask,
                                   at::Tensor asc, at::Tensor ash);
 
+std::vector<at::Tensor> gn_fwd(at::Tensor x, at::Tensor gamma,
+                               at::Tensor beta, at::Tensor res, long G,
+                               double eps, long act, bool want_mask,
+                               long path, long chunk);
+std::vector<at::Tensor> gn_bwd(at::Tensor x, at::Tensor dy, at::Tensor mean,
+                               at::Tensor rstd, at::Tensor gamma,
+                               at::Tensor mask, long G, bool want_dres,
+                               long path);
+
 std::vector<at::Tensor> maxpool_fwd(at::Tensor x, long kernel, long stride,
                                     long pad);
 at::Tensor maxpool_bwd(at::Tensor dy, at::Tensor idx, long H, long W,
@@ -133,6 +142,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bn_apply", &bn_apply);
   m.def("bn_bwd_reduce", &bn_bwd_reduce);
   m.def("bn_bwd_dx", &bn_bwd_dx);
+  m.def("gn_fwd", &gn_fwd);
+  m.def("gn_bwd", &gn_bwd);
   m.def("maxpool_fwd", &maxpool_fwd);
   m.def("maxpool_bwd", &maxpool_bwd);
   m.def("global_avg_pool", &global_avg_pool);

@@ -15,6 +15,12 @@ def build_model(name: str, num_classes: int = 10):
         return resnet50(num_classes=num_classes, stem="imagenet")
     if name == "resnet50_cifar":
         return resnet50(num_classes=num_classes, stem="cifar")
+    if name == "resnet18_gn":
+        return resnet18(num_classes=num_classes, stem="cifar", norm="gn")
+    if name == "resnet50_gn":
+        return resnet50(num_classes=num_classes, stem="imagenet", norm="gn")
+    if name == "resnet50_cifar_gn":
+        return resnet50(num_classes=num_classes, stem="cifar", norm="gn")
     if name == "mobilenet":
         return mobilenet(num_classes=num_classes)
     raise ValueError(f"unknown model {name!r}")

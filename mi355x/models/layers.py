@@ -132,6 +132,40 @@ class BatchNorm2d(nn.Module):
                               stats)
 
 
+class GroupNorm(nn.Module):
+    """GroupNorm over NHWC with optional fused residual-add + ReLU epilogue
+    (ops.group_norm lists the domain). Batch-independent: no running
+    statistics, the same in train and eval. weight and bias are [C], so a
+    state_dict interchanges with torch.nn.GroupNorm."""
+
+    def __init__(self, num_groups, num_channels, act=None, eps=1e-5):
+        super().__init__()
+        if num_groups < 1 or num_channels % num_groups:
+            raise ValueError(f"GroupNorm: num_groups={num_groups} does not "
+                             f"divide {num_channels} channels")
+        self.num_groups, self.num_channels = num_groups, num_channels
+        self.act, self.eps = act, eps
+        self.weight = nn.Parameter(torch.ones(num_channels))
+        self.bias = nn.Parameter(torch.zeros(num_channels))
+
+    def forward(self, x, residual=None):
+        return ops.group_norm(x, self.num_groups, self.weight, self.bias,
+                              residual, self.act, self.eps)
+
+
+def conv_gn_tap(conv: "Conv2d", gn: "GroupNorm", x):
+    """conv -> GroupNorm returning (out, tap): conv_bn_tap without the
+    BN-only statistics fusion. The block's shortcut consumes `tap`, so the
+    junction gradient fuses into this conv's dgrad epilogue; tap = x on CPU,
+    non-MFMA shapes and MI355X_TAP=0."""
+    if not (_tap_on() and conv.bias is None and conv.act is None):
+        return gn(conv(x)), x
+    from mi355x.ops import functional as F_
+
+    y, tap = F_.conv2d_tap(x, conv.weight, conv.stride, conv.padding)
+    return gn(y), tap
+
+
 def _fuse_stats():
     # default ON since round 2: with the shuffle-based stats fold, the
     # two-level slab reduce and the patch-kernel stats path it measures

@@ -12,24 +12,42 @@ from __future__ import annotations
 import torch
 from torch import nn
 
-from .layers import (BatchNorm2d, Conv2d, Linear, MaxPool2d, _lazy_ok,
-                     bn_conv_lazy, bn_then_conv, conv_bn, conv_bn_tap,
-                     to_model_layout)
+from .layers import (BatchNorm2d, Conv2d, GroupNorm, Linear, MaxPool2d,
+                     _lazy_ok, bn_conv_lazy, bn_then_conv, conv_bn,
+                     conv_bn_tap, conv_gn_tap, to_model_layout)
 from mi355x import ops
+
+
+def _norm(norm, gn_groups, channels, act=None):
+    """The normalisation layer of a ResNet: "bn" BatchNorm2d, "gn" GroupNorm
+    with gn_groups groups; the attribute names (bn1, ...) are shared."""
+    if norm == "bn":
+        return BatchNorm2d(channels, act=act)
+    if norm == "gn":
+        return GroupNorm(gn_groups, channels, act=act)
+    raise ValueError(f"norm={norm!r}: expected 'bn' or 'gn'")
 
 
 class BasicBlock(nn.Module):
     expansion = 1
 
-    def __init__(self, in_planes, planes, stride=1, downsample=None):
+    def __init__(self, in_planes, planes, stride=1, downsample=None,
+                 norm="bn", gn_groups=32):
         super().__init__()
+        self.gn = norm == "gn"
         self.conv1 = Conv2d(in_planes, planes, 3, stride, 1, bias=False)
-        self.bn1 = BatchNorm2d(planes, act="relu")
+        self.bn1 = _norm(norm, gn_groups, planes, "relu")
         self.conv2 = Conv2d(planes, planes, 3, 1, 1, bias=False)
-        self.bn2 = BatchNorm2d(planes, act="relu")  # fused add+relu at exit
+        # fused add+relu at exit
+        self.bn2 = _norm(norm, gn_groups, planes, "relu")
         self.downsample = downsample
 
     def forward(self, x):
+        if self.gn:  # none of the BN-only fusions; the TAP shortcut stays
+            out, tap = conv_gn_tap(self.conv1, self.bn1, x)
+            identity = (tap if self.downsample is None
+                        else self.downsample(tap))
+            return self.bn2(self.conv2(out), residual=identity)
         # lazy-BN: bn1's apply fuses into conv2's A-loads (the normalized
         # activation never materializes); conv1 carries the junction-grad
         # TAP and emits bn1's stats from its epilogue
@@ -55,17 +73,25 @@ class BasicBlock(nn.Module):
 class Bottleneck(nn.Module):
     expansion = 4
 
-    def __init__(self, in_planes, planes, stride=1, downsample=None):
+    def __init__(self, in_planes, planes, stride=1, downsample=None,
+                 norm="bn", gn_groups=32):
         super().__init__()
+        self.gn = norm == "gn"
         self.conv1 = Conv2d(in_planes, planes, 1, bias=False)
-        self.bn1 = BatchNorm2d(planes, act="relu")
+        self.bn1 = _norm(norm, gn_groups, planes, "relu")
         self.conv2 = Conv2d(planes, planes, 3, stride, 1, bias=False)
-        self.bn2 = BatchNorm2d(planes, act="relu")
+        self.bn2 = _norm(norm, gn_groups, planes, "relu")
         self.conv3 = Conv2d(planes, planes * 4, 1, bias=False)
-        self.bn3 = BatchNorm2d(planes * 4, act="relu")
+        self.bn3 = _norm(norm, gn_groups, planes * 4, "relu")
         self.downsample = downsample
 
     def forward(self, x):
+        if self.gn:  # none of the BN-only fusions; the TAP shortcut stays
+            out, tap = conv_gn_tap(self.conv1, self.bn1, x)
+            identity = (tap if self.downsample is None
+                        else self.downsample(tap))
+            out = self.bn2(self.conv2(out))
+            return self.bn3(self.conv3(out), residual=identity)
         # per-pair lazy dispatch: each internal BN fuses into its consumer
         # conv when eligible (bn_then_conv), else applies materialized —
         # one fused-stats chain either way
@@ -91,26 +117,32 @@ class Bottleneck(nn.Module):
 
 
 class Downsample(nn.Module):
-    def __init__(self, in_planes, out_planes, stride):
+    def __init__(self, in_planes, out_planes, stride, norm="bn",
+                 gn_groups=32):
         super().__init__()
+        self.gn = norm == "gn"
         self.conv = Conv2d(in_planes, out_planes, 1, stride, bias=False)
-        self.bn = BatchNorm2d(out_planes)
+        self.bn = _norm(norm, gn_groups, out_planes)
 
     def forward(self, x):
+        if self.gn:
+            return self.bn(self.conv(x))
         return conv_bn(self.conv, self.bn, x)
 
 
 class ResNet(nn.Module):
-    def __init__(self, block, layers, num_classes=10, stem="cifar"):
+    def __init__(self, block, layers, num_classes=10, stem="cifar",
+                 norm="bn", gn_groups=32):
         super().__init__()
         self.in_planes = 64
+        self.norm, self.gn_groups = norm, gn_groups
         if stem == "cifar":
             self.conv1 = Conv2d(3, 64, 3, 1, 1, bias=False)
             self.maxpool = None
         else:
             self.conv1 = Conv2d(3, 64, 7, 2, 3, bias=False)
             self.maxpool = MaxPool2d(3, 2, 1)
-        self.bn1 = BatchNorm2d(64, act="relu")
+        self.bn1 = _norm(norm, gn_groups, 64, "relu")
         self.layer1 = self._make_layer(block, 64, layers[0], 1)
         self.layer2 = self._make_layer(block, 128, layers[1], 2)
         self.layer3 = self._make_layer(block, 256, layers[2], 2)
@@ -125,15 +157,20 @@ class ResNet(nn.Module):
         downsample = None
         if stride != 1 or self.in_planes != planes * block.expansion:
             downsample = Downsample(self.in_planes, planes * block.expansion,
-                                    stride)
-        layers = [block(self.in_planes, planes, stride, downsample)]
+                                    stride, self.norm, self.gn_groups)
+        kw = dict(norm=self.norm, gn_groups=self.gn_groups)
+        layers = [block(self.in_planes, planes, stride, downsample, **kw)]
         self.in_planes = planes * block.expansion
-        layers += [block(self.in_planes, planes) for _ in range(1, blocks)]
+        layers += [block(self.in_planes, planes, **kw)
+                   for _ in range(1, blocks)]
         return nn.Sequential(*layers)
 
     def forward(self, x):
         x = to_model_layout(x)  # NCHW -> NHWC, 16-bit on GPU
-        x = conv_bn(self.conv1, self.bn1, x)
+        if self.norm == "gn":
+            x = self.bn1(self.conv1(x))
+        else:
+            x = conv_bn(self.conv1, self.bn1, x)
         if self.maxpool is not None:
             x = self.maxpool(x)
         x = self.layer1(x)
@@ -144,9 +181,14 @@ class ResNet(nn.Module):
         return self.fc(x)
 
 
-def resnet18(num_classes=10, stem="cifar"):
-    return ResNet(BasicBlock, [2, 2, 2, 2], num_classes, stem)
+def resnet18(num_classes=10, stem="cifar", norm="bn", gn_groups=32):
+    """norm="gn": every BatchNorm2d becomes a GroupNorm(gn_groups) with the
+    same activation (for small per-GPU batches, where batch statistics stop
+    working)."""
+    return ResNet(BasicBlock, [2, 2, 2, 2], num_classes, stem, norm,
+                  gn_groups)
 
 
-def resnet50(num_classes=1000, stem="imagenet"):
-    return ResNet(Bottleneck, [3, 4, 6, 3], num_classes, stem)
+def resnet50(num_classes=1000, stem="imagenet", norm="bn", gn_groups=32):
+    return ResNet(Bottleneck, [3, 4, 6, 3], num_classes, stem, norm,
+                  gn_groups)

@@ -567,6 +567,92 @@ def batch_norm(x, gamma, beta, running_mean, running_var, training,
 
 
 # ---------------------------------------------------------------------------
+# group norm (+ residual add + relu, fused)
+# ---------------------------------------------------------------------------
+
+
+def _check_group_norm(x, num_groups, gamma, beta):
+    """The GroupNorm domain (the same on both devices): every value outside
+    it is named in a ValueError."""
+    if x.dim() != 4:
+        raise ValueError(f"group_norm: x must be NHWC [N,H,W,C], got "
+                         f"{x.dim()} dimensions")
+    C, G = x.shape[-1], num_groups
+    if C % 8 != 0:
+        raise ValueError(f"group_norm: channels={C} is not a multiple of 8")
+    if not isinstance(G, int) or G < 1 or C % G != 0:
+        raise ValueError(f"group_norm: num_groups={G!r} does not divide "
+                         f"{C} channels")
+    cpg = C // G
+    if cpg & (cpg - 1):
+        raise ValueError(f"group_norm: channels per group={cpg} ({C} / {G}) "
+                         "is not a power of two")
+    if gamma.shape != (C,) or beta.shape != (C,):
+        raise ValueError(f"group_norm: gamma and beta must be [{C}], got "
+                         f"{tuple(gamma.shape)} and {tuple(beta.shape)}")
+
+
+class _GNFn(torch.autograd.Function):
+    """GroupNorm over NHWC with optional fused residual add and ReLU: the
+    two bindings of csrc/gn.hip. path / chunk (0 = auto) choose the kernel
+    path; ops.group_norm always passes auto."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, residual, num_groups, act, eps,
+                want_mask, path=0, chunk=0):
+        x = x.contiguous()
+        res = (residual.contiguous() if residual is not None
+               else torch.empty(0, device=x.device, dtype=x.dtype))
+        y, mean, rstd, mask = ext().gn_fwd(
+            x, gamma.detach().float(), beta.detach().float(), res,
+            num_groups, eps, act, want_mask, path, chunk)
+        ctx.save_for_backward(x, mean, rstd, gamma, mask)
+        ctx.conf = (num_groups, act, residual is not None, path)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, mean, rstd, gamma, mask = ctx.saved_tensors
+        G, act, has_res, path = ctx.conf
+        dy = dy.contiguous()
+        want_dres = has_res and act == _ACT_RELU
+        dx, dres, dgb = ext().gn_bwd(x, dy, mean, rstd,
+                                     gamma.detach().float(), mask, G,
+                                     want_dres, path)
+        if has_res and not want_dres:
+            dres = dy  # no activation: residual grad is dy itself
+        elif not has_res:
+            dres = None
+        return dx, dgb[1], dgb[0], dres, None, None, None, None, None, None
+
+
+def group_norm(x, num_groups, gamma, beta, residual=None, act=None,
+               eps=1e-5):
+    """GroupNorm (Wu & He 2018) over NHWC with optional fused residual-add
+    + ReLU: y = relu?((x - mean[n,g]) * rstd[n,g] * gamma[c] + beta[c]
+    (+ residual)), statistics over all pixels of the C/num_groups channels
+    of group g of sample n, biased variance. No batch statistics, so no
+    train/eval difference and no running stats.
+
+    Domain: C a multiple of 8, num_groups divides C, and C/num_groups a
+    power of two; anything else raises
+    ValueError. GPU: the kernels of csrc/gn.hip (never eager torch); under
+    torch.no_grad() no ReLU mask is written."""
+    _check_group_norm(x, num_groups, gamma, beta)
+    a = _ACT_RELU if act == "relu" else _ACT_NONE
+    if x.is_cuda:
+        return _GNFn.apply(x, gamma, beta, residual, num_groups, a,
+                           float(eps), torch.is_grad_enabled())
+    y = F.group_norm(x.permute(0, 3, 1, 2).float(), num_groups, gamma, beta,
+                     eps).permute(0, 2, 3, 1)
+    if residual is not None:
+        y = y + residual
+    if a == _ACT_RELU:
+        y = F.relu(y)
+    return y
+
+
+# ---------------------------------------------------------------------------
 # pooling
 # ---------------------------------------------------------------------------
 
