@@ -75,6 +75,17 @@ std::vector<at::Tensor> gn_bwd(at::Tensor x, at::Tensor dy, at::Tensor mean,
                                at::Tensor mask, long G, bool want_dres,
                                long path);
 
+std::vector<at::Tensor> se_fwd(at::Tensor x, at::Tensor w1, at::Tensor b1,
+                               at::Tensor w2t, at::Tensor b2, at::Tensor res,
+                               long act, bool want_side, long path,
+                               long chunk);
+std::vector<at::Tensor> se_bwd(at::Tensor x, at::Tensor dy, at::Tensor mask,
+                               at::Tensor z, at::Tensor g, at::Tensor w1,
+                               at::Tensor w2t, bool want_dres, long path,
+                               long chunk);
+std::vector<at::Tensor> se_wgrad(at::Tensor s, at::Tensor z, at::Tensor dl,
+                                 at::Tensor dz);
+
 std::vector<at::Tensor> maxpool_fwd(at::Tensor x, long kernel, long stride,
                                     long pad);
 at::Tensor maxpool_bwd(at::Tensor dy, at::Tensor idx, long H, long W,
@@ -144,6 +155,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bn_bwd_dx", &bn_bwd_dx);
   m.def("gn_fwd", &gn_fwd);
   m.def("gn_bwd", &gn_bwd);
+  m.def("se_fwd", &se_fwd);
+  m.def("se_bwd", &se_bwd);
+  m.def("se_wgrad", &se_wgrad);
   m.def("maxpool_fwd", &maxpool_fwd);
   m.def("maxpool_bwd", &maxpool_bwd);
   m.def("global_avg_pool", &global_avg_pool);

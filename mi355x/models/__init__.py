@@ -21,6 +21,12 @@ def build_model(name: str, num_classes: int = 10):
         return resnet50(num_classes=num_classes, stem="imagenet", norm="gn")
     if name == "resnet50_cifar_gn":
         return resnet50(num_classes=num_classes, stem="cifar", norm="gn")
+    if name == "se_resnet18":
+        return resnet18(num_classes=num_classes, stem="cifar", se=16)
+    if name == "se_resnet50":
+        return resnet50(num_classes=num_classes, stem="imagenet", se=16)
+    if name == "se_resnet50_cifar":
+        return resnet50(num_classes=num_classes, stem="cifar", se=16)
     if name == "mobilenet":
         return mobilenet(num_classes=num_classes)
     raise ValueError(f"unknown model {name!r}")

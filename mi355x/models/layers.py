@@ -153,6 +153,27 @@ class GroupNorm(nn.Module):
                               residual, self.act, self.eps)
 
 
+class SqueezeExcite(nn.Module):
+    """Squeeze-and-excitation gate (Hu et al. 2018) over NHWC with optional
+    fused residual-add + ReLU epilogue (ops.squeeze_excite lists the
+    domain). fc1 and fc2 only hold the parameters: the whole block is one
+    op."""
+
+    def __init__(self, channels, reduction=16, act=None):
+        super().__init__()
+        if reduction < 1 or channels // reduction < 1:
+            raise ValueError(f"SqueezeExcite: reduction={reduction} leaves "
+                             f"no hidden unit for {channels} channels")
+        self.channels, self.reduction, self.act = channels, reduction, act
+        self.fc1 = Linear(channels, channels // reduction)
+        self.fc2 = Linear(channels // reduction, channels)
+
+    def forward(self, x, residual=None):
+        return ops.squeeze_excite(x, self.fc1.weight, self.fc1.bias,
+                                  self.fc2.weight, self.fc2.bias, residual,
+                                  self.act)
+
+
 def conv_gn_tap(conv: "Conv2d", gn: "GroupNorm", x):
     """conv -> GroupNorm returning (out, tap): conv_bn_tap without the
     BN-only statistics fusion. The block's shortcut consumes `tap`, so the

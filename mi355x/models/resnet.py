@@ -13,8 +13,8 @@ import torch
 from torch import nn
 
 from .layers import (BatchNorm2d, Conv2d, GroupNorm, Linear, MaxPool2d,
-                     _lazy_ok, bn_conv_lazy, bn_then_conv, conv_bn,
-                     conv_bn_tap, conv_gn_tap, to_model_layout)
+                     SqueezeExcite, _lazy_ok, bn_conv_lazy, bn_then_conv,
+                     conv_bn, conv_bn_tap, conv_gn_tap, to_model_layout)
 from mi355x import ops
 
 
@@ -32,17 +32,28 @@ class BasicBlock(nn.Module):
     expansion = 1
 
     def __init__(self, in_planes, planes, stride=1, downsample=None,
-                 norm="bn", gn_groups=32):
+                 norm="bn", gn_groups=32, se=None):
         super().__init__()
         self.gn = norm == "gn"
         self.conv1 = Conv2d(in_planes, planes, 3, stride, 1, bias=False)
         self.bn1 = _norm(norm, gn_groups, planes, "relu")
         self.conv2 = Conv2d(planes, planes, 3, 1, 1, bias=False)
-        # fused add+relu at exit
-        self.bn2 = _norm(norm, gn_groups, planes, "relu")
+        # fused add+relu at exit: in bn2, or in the SE gate behind it
+        self.bn2 = _norm(norm, gn_groups, planes, None if se else "relu")
         self.downsample = downsample
+        self.se = SqueezeExcite(planes, se, act="relu") if se else None
 
     def forward(self, x):
+        if self.se is not None:
+            # the gate takes over bn2's residual add and ReLU; the TAP
+            # shortcut stays, the lazy-BN path is not taken
+            tap_fn = conv_gn_tap if self.gn else conv_bn_tap
+            out, tap = tap_fn(self.conv1, self.bn1, x)
+            identity = (tap if self.downsample is None
+                        else self.downsample(tap))
+            out = (self.bn2(self.conv2(out)) if self.gn
+                   else conv_bn(self.conv2, self.bn2, out))
+            return self.se(out, residual=identity)
         if self.gn:  # none of the BN-only fusions; the TAP shortcut stays
             out, tap = conv_gn_tap(self.conv1, self.bn1, x)
             identity = (tap if self.downsample is None
@@ -74,7 +85,7 @@ class Bottleneck(nn.Module):
     expansion = 4
 
     def __init__(self, in_planes, planes, stride=1, downsample=None,
-                 norm="bn", gn_groups=32):
+                 norm="bn", gn_groups=32, se=None):
         super().__init__()
         self.gn = norm == "gn"
         self.conv1 = Conv2d(in_planes, planes, 1, bias=False)
@@ -82,10 +93,26 @@ class Bottleneck(nn.Module):
         self.conv2 = Conv2d(planes, planes, 3, stride, 1, bias=False)
         self.bn2 = _norm(norm, gn_groups, planes, "relu")
         self.conv3 = Conv2d(planes, planes * 4, 1, bias=False)
-        self.bn3 = _norm(norm, gn_groups, planes * 4, "relu")
+        self.bn3 = _norm(norm, gn_groups, planes * 4,
+                         None if se else "relu")
         self.downsample = downsample
+        self.se = (SqueezeExcite(planes * 4, se, act="relu") if se
+                   else None)
 
     def forward(self, x):
+        if self.se is not None:
+            # the gate takes over bn3's residual add and ReLU; the TAP
+            # shortcut stays, the lazy-BN path is not taken
+            tap_fn = conv_gn_tap if self.gn else conv_bn_tap
+            out, tap = tap_fn(self.conv1, self.bn1, x)
+            identity = (tap if self.downsample is None
+                        else self.downsample(tap))
+            if self.gn:
+                out = self.bn3(self.conv3(self.bn2(self.conv2(out))))
+            else:
+                out = conv_bn(self.conv2, self.bn2, out)
+                out = conv_bn(self.conv3, self.bn3, out)
+            return self.se(out, residual=identity)
         if self.gn:  # none of the BN-only fusions; the TAP shortcut stays
             out, tap = conv_gn_tap(self.conv1, self.bn1, x)
             identity = (tap if self.downsample is None
@@ -132,10 +159,10 @@ class Downsample(nn.Module):
 
 class ResNet(nn.Module):
     def __init__(self, block, layers, num_classes=10, stem="cifar",
-                 norm="bn", gn_groups=32):
+                 norm="bn", gn_groups=32, se=None):
         super().__init__()
         self.in_planes = 64
-        self.norm, self.gn_groups = norm, gn_groups
+        self.norm, self.gn_groups, self.se = norm, gn_groups, se
         if stem == "cifar":
             self.conv1 = Conv2d(3, 64, 3, 1, 1, bias=False)
             self.maxpool = None
@@ -158,7 +185,7 @@ class ResNet(nn.Module):
         if stride != 1 or self.in_planes != planes * block.expansion:
             downsample = Downsample(self.in_planes, planes * block.expansion,
                                     stride, self.norm, self.gn_groups)
-        kw = dict(norm=self.norm, gn_groups=self.gn_groups)
+        kw = dict(norm=self.norm, gn_groups=self.gn_groups, se=self.se)
         layers = [block(self.in_planes, planes, stride, downsample, **kw)]
         self.in_planes = planes * block.expansion
         layers += [block(self.in_planes, planes, **kw)
@@ -181,14 +208,17 @@ class ResNet(nn.Module):
         return self.fc(x)
 
 
-def resnet18(num_classes=10, stem="cifar", norm="bn", gn_groups=32):
+def resnet18(num_classes=10, stem="cifar", norm="bn", gn_groups=32, se=None):
     """norm="gn": every BatchNorm2d becomes a GroupNorm(gn_groups) with the
     same activation (for small per-GPU batches, where batch statistics stop
-    working)."""
+    working). se=16: SE-ResNet (Hu et al. 2018), a SqueezeExcite gate with
+    that reduction behind each block's last norm; the gate takes over the
+    block's residual add and ReLU."""
     return ResNet(BasicBlock, [2, 2, 2, 2], num_classes, stem, norm,
-                  gn_groups)
+                  gn_groups, se)
 
 
-def resnet50(num_classes=1000, stem="imagenet", norm="bn", gn_groups=32):
+def resnet50(num_classes=1000, stem="imagenet", norm="bn", gn_groups=32,
+             se=None):
     return ResNet(Bottleneck, [3, 4, 6, 3], num_classes, stem, norm,
-                  gn_groups)
+                  gn_groups, se)

@@ -653,6 +653,118 @@ def group_norm(x, num_groups, gamma, beta, residual=None, act=None,
 
 
 # ---------------------------------------------------------------------------
+# squeeze-and-excitation (+ residual add + relu, fused)
+# ---------------------------------------------------------------------------
+
+
+def _check_squeeze_excite(x, w1, b1, w2, b2, residual):
+    """The squeeze_excite domain (the same on both devices): every value
+    outside it is named in a ValueError."""
+    if x.dim() != 4:
+        raise ValueError(f"squeeze_excite: x must be NHWC [N,H,W,C], got "
+                         f"{x.dim()} dimensions")
+    C = x.shape[-1]
+    if C % 8 != 0 or not 8 <= C <= 2048:
+        raise ValueError(f"squeeze_excite: channels={C} is not a multiple "
+                         "of 8 in [8, 2048]")
+    if w1.dim() != 2 or w1.shape[1] != C:
+        raise ValueError(f"squeeze_excite: w1 must be [Cr,{C}], got "
+                         f"{tuple(w1.shape)}")
+    Cr = w1.shape[0]
+    if not 1 <= Cr <= 256:
+        raise ValueError(f"squeeze_excite: reduced channels={Cr} not in "
+                         "[1, 256]")
+    for name, t, shape in (("b1", b1, (Cr,)), ("w2", w2, (C, Cr)),
+                           ("b2", b2, (C,))):
+        if tuple(t.shape) != shape:
+            raise ValueError(f"squeeze_excite: {name} must be "
+                             f"{list(shape)}, got {tuple(t.shape)}")
+    if residual is not None and (residual.shape != x.shape
+                                 or residual.dtype != x.dtype):
+        raise ValueError(f"squeeze_excite: residual "
+                         f"{tuple(residual.shape)} {residual.dtype} must "
+                         f"match x {tuple(x.shape)} {x.dtype}")
+
+
+def _w32_t(weight: torch.Tensor) -> torch.Tensor:
+    """fp32 [C,Cr] parameter -> cached fp32 [Cr,C] transpose (the SE
+    kernels read every weight along C)."""
+    key = (weight._version, _cache_epoch)
+    cache = getattr(weight, "_mi355x_w32t", None)
+    if cache is not None and cache[0] == key:
+        return cache[1]
+    wt = weight.detach().float().t().contiguous()
+    weight._mi355x_w32t = (key, wt)
+    return wt
+
+
+class _SEFn(torch.autograd.Function):
+    """Squeeze-and-excitation over NHWC with optional fused residual add
+    and ReLU: the bindings of csrc/se.hip. path / chunk (0 = auto) choose
+    the kernel path; ops.squeeze_excite always passes auto."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2, residual, act, want_side, path=0,
+                chunk=0):
+        x = x.contiguous()
+        res = (residual.contiguous() if residual is not None
+               else torch.empty(0, device=x.device, dtype=x.dtype))
+        w1f = w1.detach().float().contiguous()
+        w2t = _w32_t(w2)
+        y, s, z, g, mask = ext().se_fwd(
+            x, w1f, b1.detach().float(), w2t, b2.detach().float(), res, act,
+            want_side, path, chunk)
+        ctx.save_for_backward(x, s, z, g, mask, w1f, w2t)
+        ctx.conf = (act, residual is not None, path, chunk)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, s, z, g, mask, w1f, w2t = ctx.saved_tensors
+        act, has_res, path, chunk = ctx.conf
+        dy = dy.contiguous()
+        want_dres = has_res and act == _ACT_RELU
+        dx, dres, dl, dz = ext().se_bwd(x, dy, mask, z, g, w1f, w2t,
+                                        want_dres, path, chunk)
+        dw1, db1, dw2, db2 = ext().se_wgrad(s, z, dl, dz)
+        if has_res and not want_dres:
+            dres = dy  # no activation: residual grad is dy itself
+        elif not has_res:
+            dres = None
+        return dx, dw1, db1, dw2, db2, dres, None, None, None, None
+
+
+def squeeze_excite(x, w1, b1, w2, b2, residual=None, act=None):
+    """Squeeze-and-excitation (Hu et al. 2018) over NHWC with optional
+    fused residual-add + ReLU:
+
+        s[n,c] = mean over h,w of x[n,h,w,c]
+        z[n,j] = relu(sum_c w1[j,c] * s[n,c] + b1[j])
+        g[n,c] = sigmoid(sum_j w2[c,j] * z[n,j] + b2[c])
+        y      = act(x * g[n,c] + residual)
+
+    w1 [Cr,C], b1 [Cr], w2 [C,Cr], b2 [C] are fp32 parameters. Domain: x
+    4-d, C a multiple of 8 in [8, 2048], Cr in [1, 256], residual of x's
+    shape and dtype; anything else raises ValueError. GPU: the kernels of
+    csrc/se.hip (never eager torch); under torch.no_grad() no ReLU mask and
+    no side outputs are written."""
+    _check_squeeze_excite(x, w1, b1, w2, b2, residual)
+    a = _ACT_RELU if act == "relu" else _ACT_NONE
+    if x.is_cuda:
+        return _SEFn.apply(x, w1, b1, w2, b2, residual, a,
+                           torch.is_grad_enabled())
+    s = x.float().mean(dim=(1, 2))
+    z = F.relu(F.linear(s, w1, b1))
+    g = torch.sigmoid(F.linear(z, w2, b2))
+    y = x.float() * g[:, None, None, :]
+    if residual is not None:
+        y = y + residual
+    if a == _ACT_RELU:
+        y = F.relu(y)
+    return y
+
+
+# ---------------------------------------------------------------------------
 # pooling
 # ---------------------------------------------------------------------------
 

@@ -26,6 +26,7 @@ SRC = [
     "mi355x/csrc/wcast.hip",
     "mi355x/csrc/bn.hip",
     "mi355x/csrc/gn.hip",
+    "mi355x/csrc/se.hip",
     "mi355x/csrc/pool.hip",
     "mi355x/csrc/gemm.hip",
     "mi355x/csrc/gemm_mfma.hip",
