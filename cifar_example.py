@@ -25,12 +25,16 @@ Env overrides (benchmark configs; CLI shape unchanged):
   MI355X_FP16=1 MI355X_DEVICE_SCALER=1      fp16 compute with
                                             amp.DeviceGradScaler: dynamic loss
                                             scaling, no host sync per step
-  MI355X_OPTIM=sgd|lars                     optimizer (default sgd); lars is
-                                            optim.LARS, for large batches
+  MI355X_OPTIM=sgd|lars|adamw|lamb          optimizer (default sgd); lars is
+                                            optim.LARS, for large batches;
+                                            adamw and lamb are the adaptive
+                                            optim.AdamW and optim.LAMB
   MI355X_LARS_ETA=<float>                   LARS trust coefficient (default
                                             0.001)
-  MI355X_WD=<float>                         weight decay of either optimizer
-                                            (default 0)
+  MI355X_BETA1=<float> MI355X_BETA2=<float> betas of adamw / lamb (default
+                                            0.9 / 0.999)
+  MI355X_WD=<float>                         weight decay of whichever
+                                            optimizer is built (default 0)
   MI355X_LABEL_SMOOTH=<float>               label smoothing of the training
                                             loss (default 0)
   MI355X_CUTMIX=<p> MI355X_MIXUP=<p>        probability that a train sample is

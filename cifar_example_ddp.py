@@ -26,9 +26,12 @@ MI355X_AUGMENT=1 (pad-4 random crop + flip on the train loader; needs
 MI355X_DEVICE_DATA), MI355X_CLIP_NORM=<float> (global-norm gradient
 clipping in the fused step; unset or 0 = off), MI355X_DEVICE_SCALER=1
 (with MI355X_FP16=1: amp.DeviceGradScaler, loss scaling without a host
-sync per step), MI355X_OPTIM=sgd|lars (default sgd; lars is optim.LARS, for
-large batches), MI355X_LARS_ETA=<float> (LARS trust coefficient, default
-0.001), MI355X_WD=<float> (weight decay of either optimizer, default 0),
+sync per step), MI355X_OPTIM=sgd|lars|adamw|lamb (default sgd; lars is
+optim.LARS, for large batches; adamw and lamb are the adaptive optim.AdamW
+and optim.LAMB), MI355X_LARS_ETA=<float> (LARS trust coefficient, default
+0.001), MI355X_BETA1=<float> / MI355X_BETA2=<float> (betas of adamw / lamb,
+default 0.9 / 0.999), MI355X_WD=<float> (weight decay of whichever optimizer
+is built, default 0),
 MI355X_LABEL_SMOOTH=<float> (label smoothing of the training loss, default
 0), MI355X_CUTMIX=<p> / MI355X_MIXUP=<p> (probability that a train sample
 is cutmixed / mixed up with its partner in the rank's batch, default 0;

@@ -27,6 +27,18 @@ void lars_step(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor table,
                c10::optional<at::Tensor> lr_dev, double lr, double mu,
                double wd, double gscale, double max_norm,
                c10::optional<at::Tensor> ema, c10::optional<at::Tensor> clock);
+void adam_step(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v,
+               at::Tensor table, at::Tensor tens, at::Tensor state,
+               at::Tensor stats, at::Tensor clock,
+               c10::optional<at::Tensor> lr_dev, double lr, double b1,
+               double b2, double eps, double wd, double gscale,
+               double max_norm, c10::optional<at::Tensor> ema);
+void lamb_step(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v,
+               at::Tensor table, at::Tensor tens, at::Tensor slab,
+               at::Tensor state, at::Tensor stats, at::Tensor clock,
+               c10::optional<at::Tensor> lr_dev, double lr, double b1,
+               double b2, double eps, double wd, double gscale,
+               double max_norm, c10::optional<at::Tensor> ema);
 at::Tensor cast_to_16(at::Tensor src, at::Tensor like);
 at::Tensor cast_permute_krsc(at::Tensor w, at::Tensor like);
 at::Tensor cast_permute_krsc_pad(at::Tensor w, at::Tensor like);
@@ -138,6 +150,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("clock_advance", &clock_advance);
   m.def("lars_stats", &lars_stats);
   m.def("lars_step", &lars_step);
+  m.def("adam_step", &adam_step);
+  m.def("lamb_step", &lamb_step);
   m.def("cast_to_16", &cast_to_16);
   m.def("cast_permute_krsc", &cast_permute_krsc);
   m.def("cast_permute_krsc_pad", &cast_permute_krsc_pad);

@@ -15,6 +15,7 @@ extension (no silent PyTorch fallback on GPU).
 
 from __future__ import annotations
 
+import math
 from typing import NamedTuple
 
 import numpy as np
@@ -1455,6 +1456,130 @@ def lars_step(flat_param, flat_grad, flat_momentum, plan, state, lr,
                                      else lr))
     if ema is not None:
         _ema_update_cpu(ema, flat_param, clock)
+
+
+# ---------------------------------------------------------------------------
+# AdamW and LAMB over the flat buffers, on the LARS tile plan
+# ---------------------------------------------------------------------------
+
+LAMB_WNORM, LAMB_UNORM, LAMB_TRUST = 0, 1, 2  # columns of plan.stats
+
+
+def _ipow(b, t):
+    """b**t by squaring in double: adam.hip's ipow, multiplication for
+    multiplication."""
+    r = 1.0
+    while t > 0:
+        if t & 1:
+            r *= b
+        b *= b
+        t >>= 1
+    return r
+
+
+def _adaptive_step(who, flat_param, flat_grad, exp_avg, exp_avg_sq, plan,
+                   state, clock, lr, betas, eps, weight_decay, grad_scale,
+                   max_norm, ema):
+    lamb = who == "lamb_step"
+    max_norm = float(max_norm)
+    b1, b2 = (float(b) for b in betas)
+    for name, b in (("beta1", b1), ("beta2", b2)):
+        if not 0.0 <= b < 1.0:
+            raise ValueError(f"{who}: {name} must be in [0, 1), got {b}")
+    if not eps >= 0.0:
+        raise ValueError(f"{who}: eps must be >= 0, got {eps}")
+    if not weight_decay >= 0.0:
+        raise ValueError(f"{who}: weight_decay must be >= 0, got "
+                         f"{weight_decay}")
+    plan.check(flat_param, flat_grad, exp_avg, exp_avg_sq)
+    lr_t = _lr_tensor(lr, flat_param, who)
+    if (clock is None or clock.numel() < CK_LEN
+            or clock.dtype != torch.float32
+            or clock.device != flat_param.device):
+        raise ValueError(f"{who}: needs the step clock, float32[{CK_LEN}] on "
+                         "the buffers' device (bias correction reads it)")
+    _check_ema(ema, clock, flat_param, who)
+    if flat_param.is_cuda:
+        args = (state, plan.stats, clock, lr_t,
+                0.0 if lr_t is not None else lr, b1, b2, eps, weight_decay,
+                grad_scale, max_norm, ema)
+        if lamb:
+            ext().lamb_step(flat_param, flat_grad, exp_avg, exp_avg_sq,
+                            plan.table, plan.tens, plan.slab, *args)
+        else:
+            ext().adam_step(flat_param, flat_grad, exp_avg, exp_avg_sq,
+                            plan.table, plan.tens, *args)
+        return
+    if int(state.view(torch.int32)[GS_NONFINITE]) != 0:
+        return
+    _, _, eff = _guard_coef(state, grad_scale, max_norm)
+    t = max(int(clock.view(torch.int32)[CK_STEP]), 0) + 1
+    rbc1 = 1.0 / (1.0 - _ipow(b1, t))
+    rsbc2 = 1.0 / math.sqrt(1.0 - _ipow(b2, t))
+    # float32, one rounding per op, in adam.hip's order
+    g = flat_grad.mul(eff)
+    exp_avg.mul_(b1).add_(g * (1.0 - b1))
+    exp_avg_sq.mul_(b2).add_(g * (1.0 - b2) * g)
+    wd = torch.where(plan._excluded, 0.0, float(weight_decay)).float()
+    den = exp_avg_sq.sqrt().mul_(rsbc2).add_(eps)
+    u = (exp_avg * rbc1).div_(den).add_(plan.per_element(wd) * flat_param)
+    step = lr_t.reshape(()) if lr_t is not None else lr
+    if lamb:
+        S = len(plan.exclude)
+        sums = torch.zeros(S, 2, dtype=torch.float64)
+        for s, (a, b) in enumerate(zip(plan.offsets, plan.offsets[1:])):
+            sums[s, 0] = flat_param[a:b].double().square().sum()
+            sums[s, 1] = u[a:b].double().square().sum()
+        wn, un = sums[:, 0].sqrt().float(), sums[:, 1].sqrt().float()
+        keep = (wn > 0) & (un > 0) & ~plan._excluded
+        plan.stats[:, LAMB_WNORM] = wn
+        plan.stats[:, LAMB_UNORM] = un
+        plan.stats[:, LAMB_TRUST] = torch.where(keep, wn / un,
+                                                torch.ones_like(wn))
+        step = plan.per_element(plan.stats[:, LAMB_TRUST] * step)
+    flat_param.sub_(u * step)
+    if ema is not None:
+        _ema_update_cpu(ema, flat_param, clock)
+
+
+def adam_step(flat_param, flat_grad, exp_avg, exp_avg_sq, plan, state, clock,
+              lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
+              grad_scale=1.0, max_norm=float("inf"), ema=None):
+    """AdamW over the flat buffers after grad_stats filled ``state[4:6]``.
+    With g = g_raw * eff (the guarded steps' multiplier) and t =
+    ``clock[CK_STEP]`` + 1, the applied steps so far plus this one:
+
+        m = b1*m + (1-b1)*g             v = b2*v + (1-b2)*g*g
+        u = (m / (1-b1^t)) / (sqrt(v / (1-b2^t)) + eps) + wd_s * w
+        w -= lr * u                     (wd_s = 0 for an excluded tensor)
+
+    and nothing written at all if the gradient holds an inf/nan. ``plan`` is
+    a lars_plan of the buffers (it carries the exclusions). ``clock`` is the
+    optimizer's step clock: the bias correction is computed from it on the
+    device, so a skipped step (clock_advance stands still) does not move t.
+    ``lr`` and ``ema`` as in lars_step. One kernel: 4 reads and 3 writes per
+    element (5 and 4 with an EMA)."""
+    _adaptive_step("adam_step", flat_param, flat_grad, exp_avg, exp_avg_sq,
+                   plan, state, clock, lr, betas, eps, weight_decay,
+                   grad_scale, max_norm, ema)
+
+
+def lamb_step(flat_param, flat_grad, exp_avg, exp_avg_sq, plan, state, clock,
+              lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
+              grad_scale=1.0, max_norm=float("inf"), ema=None):
+    """LAMB (You et al. 2020): adam_step's m, v and u, then per tensor
+
+        trust_s = ||w_s|| / ||u_s||     (1 for an excluded tensor, or if
+        w -= lr * trust_s * u            either norm is 0)
+
+    with {||w_s||, ||u_s||, trust_s} left in ``plan.stats`` (a skipped step
+    leaves them as they were). GPU: a moments pass that writes m and v and
+    reduces w^2 and u^2 per tile, a one-block fixed-order combine in double,
+    and an apply pass that recomputes u from the stored moments: 6 reads and
+    4 writes per element, bit-identical from run to run."""
+    _adaptive_step("lamb_step", flat_param, flat_grad, exp_avg, exp_avg_sq,
+                   plan, state, clock, lr, betas, eps, weight_decay,
+                   grad_scale, max_norm, ema)
 
 
 # ---------------------------------------------------------------------------

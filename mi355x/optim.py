@@ -16,6 +16,10 @@ LARS is the large-batch optimizer over the same buffers: per-tensor trust
 ratios from a tile reduction that respects tensor boundaries in the flat
 layout (mi355x/csrc/lars.hip), always guarded.
 
+AdamW and LAMB are the adaptive pair over the same buffers and the same
+tile plan (mi355x/csrc/adam.hip), always guarded; their step count for the
+bias correction is the device-side step clock, never a host counter.
+
 LRSchedule and EMA ride on a step clock the optimizer keeps on the device
 (layout: mi355x/csrc/gradstat.hip): a count of the steps that were applied,
 the learning rate the next one uses and the weight of the next EMA update.
@@ -175,12 +179,14 @@ class _Clocked:
     """What optim.SGD and optim.LARS share: the step clock behind an
     LRSchedule and an EMA, and its part of the checkpoint."""
 
-    def _init_clock(self, lr, ema):
+    def _init_clock(self, lr, ema, force=False):
+        """``force``: keep a clock even with no schedule and no EMA (AdamW
+        and LAMB read the step count from it); ``self.lr`` stays the float."""
         self.schedule = lr if isinstance(lr, LRSchedule) else None
         self.ema = ema
         self.clock = None
         self.lr = lr
-        if self.schedule is None and ema is None:
+        if self.schedule is None and ema is None and not force:
             return
         dev = self.flat.flat_param.device
         if ema is not None:
@@ -188,7 +194,7 @@ class _Clocked:
         if self.schedule is not None:
             self._table = self.schedule.values.to(dev)
         else:
-            # the clock only counts for the EMA: its lr slot is not read
+            # the clock only counts steps: its lr slot is not read
             self._table = torch.zeros(1, dtype=torch.float32, device=dev)
         self.clock = _fn.new_clock(dev, self._table, *self._ema_args())
         if self.schedule is not None:
@@ -457,16 +463,141 @@ class LARS(_Clocked):
         self._load_clock(sd)
 
 
+class AdamW(_Clocked):
+    """AdamW (Loshchilov & Hutter 2019) over the flat buffers, one HIP
+    kernel per step (mi355x/csrc/adam.hip). With g the true (unscaled,
+    averaged, clipped) gradient and t the applied steps so far plus one:
+
+        m = b1*m + (1-b1)*g;   v = b2*v + (1-b2)*g*g
+        u = (m / (1-b1^t)) / (sqrt(v / (1-b2^t)) + eps) + wd * w
+        w -= lr * u
+
+    which is torch.optim.AdamW when nothing is excluded. Excluded tensors
+    (default: ndim <= 1; or an ``exclude`` predicate on the parameter) take
+    no weight decay. m is ``flat.flat_momentum``, v the float32
+    ``exp_avg_sq`` this object allocates. No amsgrad, no 16-bit state.
+
+    Every step is guarded: grad_stats over the gradient first, and on an
+    inf/nan nothing is written. t is the optimizer's step clock, advanced on
+    the device only by applied steps, so a skipped step moves neither the
+    bias correction nor the schedule nor the EMA, in a captured graph too.
+    ``lr`` and ``ema`` as in optim.LARS."""
+
+    _update = staticmethod(ops.adam_step)
+
+    def __init__(self, flat: FlatState, lr, betas=(0.9, 0.999),
+                 eps: float = 1e-8, weight_decay: float = 1e-2, exclude=None,
+                 grad_scale: float = 1.0, max_grad_norm: float | None = None,
+                 ema: EMA | None = None):
+        self.flat = flat
+        self._init_clock(lr, ema, force=True)
+        self.betas = (float(betas[0]), float(betas[1]))
+        self.eps = eps
+        self.weight_decay = weight_decay
+        self.grad_scale = grad_scale
+        self.max_grad_norm = max_grad_norm
+        if exclude is None:
+            exclude = lambda p: p.ndim <= 1  # noqa: E731
+        spans = [flat.offsets[id(p)] for p in flat.params]
+        self.plan = ops.lars_plan(
+            [0] + [e for _, e in spans], [bool(exclude(p)) for p in flat.params],
+            flat.flat_param.device)
+        self.exp_avg_sq = torch.zeros_like(flat.flat_param)
+        self._own_state = None    # made on first use without a scaler
+        self._slab = None         # grad_stats' partials, GPU only
+        self._guard_state = None  # the state the last step used
+
+    def step(self, scaler=None):
+        f = self.flat
+        g = f.flat_grad
+        if scaler is not None:
+            state = scaler.state
+            dyn = (scaler.growth_factor, scaler.backoff_factor,
+                   scaler.growth_interval)
+        else:
+            if self._own_state is None:
+                self._own_state = _fn.new_guard_state(g.device)
+            state = self._own_state
+            dyn = (1.0, 1.0, 0)  # no loss scale to move
+        if g.is_cuda and self._slab is None:
+            self._slab = torch.empty(_fn.GRAD_STATS_SLAB, dtype=torch.float32,
+                                     device=g.device)
+        self._guard_state = state
+        max_norm = (float("inf") if self.max_grad_norm is None
+                    else float(self.max_grad_norm))
+        ops.grad_stats(g, slab=self._slab,
+                       out=state[_fn.GS_NONFINITE:_fn.GS_RAW_NORM + 1])
+        self._update(f.flat_param, g, f.flat_momentum, self.exp_avg_sq,
+                     self.plan, state, self.clock, self.lr, self.betas,
+                     self.eps, self.weight_decay, self.grad_scale, max_norm,
+                     ema=None if self.ema is None else self.ema.flat_ema)
+        ops.scaler_update(state, self.grad_scale, max_norm, *dyn)
+        self._advance_clock(state)
+        _fn.bump_cache_epoch()  # invalidate cached 16-bit weight copies
+
+    last_grad_norm = LARS.last_grad_norm
+    skipped_steps = LARS.skipped_steps
+
+    def zero_grad(self, set_to_none: bool = False):
+        self.flat.zero_grad()
+
+    def state_dict(self):
+        return {"exp_avg": self.flat.flat_momentum,
+                "exp_avg_sq": self.exp_avg_sq, "lr": float(self.lr),
+                "betas": self.betas, "eps": self.eps,
+                "weight_decay": self.weight_decay,
+                "max_grad_norm": self.max_grad_norm,
+                **self._clock_state_dict()}
+
+    def load_state_dict(self, sd):
+        self.flat.flat_momentum.copy_(sd["exp_avg"])
+        self.exp_avg_sq.copy_(sd["exp_avg_sq"])
+        self._load_lr(sd)
+        self.betas = tuple(float(b) for b in sd["betas"])
+        self.eps = sd["eps"]
+        self.weight_decay = sd["weight_decay"]
+        self.max_grad_norm = sd["max_grad_norm"]
+        self._load_clock(sd)
+
+
+class LAMB(AdamW):
+    """LAMB (You et al. 2020), the adaptive sibling of LARS for very large
+    batches: AdamW's m, v and u, then per tensor s
+
+        trust_s = ||w_s|| / ||u_s||;   w -= lr * trust_s * u
+
+    Excluded tensors, and tensors whose weights or update are all zero,
+    take trust 1. Two passes over the tile plan and a one-block combine in
+    between (mi355x/csrc/adam.hip); bit-identical from run to run.
+    Arguments, guard, clock and checkpoint as optim.AdamW."""
+
+    _update = staticmethod(ops.lamb_step)
+
+    @property
+    def last_trust_ratios(self):
+        """trust_s of the last applied step, one per tensor in flat.params
+        order: a device tensor, no sync. All 1 before the first step."""
+        return self.plan.stats[:, _fn.LAMB_TRUST]
+
+
 def from_env(flat: FlatState, lr, momentum: float = 0.9,
              grad_scale: float = 1.0, max_grad_norm: float | None = None,
              ema: EMA | None = None):
-    """The training scripts' optimizer: MI355X_OPTIM=sgd|lars (default sgd),
-    MI355X_WD (weight decay, default 0) and, for LARS, MI355X_LARS_ETA (the
-    trust coefficient, default 0.001). ``lr`` is a float or an LRSchedule
+    """The training scripts' optimizer: MI355X_OPTIM=sgd|lars|adamw|lamb
+    (default sgd), MI355X_WD (weight decay, default 0), for LARS
+    MI355X_LARS_ETA (the trust coefficient, default 0.001), for AdamW and
+    LAMB MI355X_BETA1 / MI355X_BETA2 (defaults 0.9 / 0.999; ``momentum`` is
+    not used by these two). ``lr`` is a float or an LRSchedule
     (schedule_from_env), ``ema`` an optim.EMA or None (ema_from_env).
     ValueError for any other MI355X_OPTIM."""
     kind = os.environ.get("MI355X_OPTIM", "sgd")
     wd = float(os.environ.get("MI355X_WD", "0"))
+    if kind in ("adamw", "lamb"):
+        betas = (float(os.environ.get("MI355X_BETA1", "0.9")),
+                 float(os.environ.get("MI355X_BETA2", "0.999")))
+        return (AdamW if kind == "adamw" else LAMB)(
+            flat, lr=lr, betas=betas, weight_decay=wd, grad_scale=grad_scale,
+            max_grad_norm=max_grad_norm, ema=ema)
     if kind == "sgd":
         return SGD(flat, lr=lr, momentum=momentum, weight_decay=wd,
                    grad_scale=grad_scale, max_grad_norm=max_grad_norm,
@@ -476,7 +607,8 @@ def from_env(flat: FlatState, lr, momentum: float = 0.9,
         return LARS(flat, lr=lr, momentum=momentum, weight_decay=wd,
                     trust_coefficient=eta, grad_scale=grad_scale,
                     max_grad_norm=max_grad_norm, ema=ema)
-    raise ValueError(f"MI355X_OPTIM={kind}: expected sgd or lars")
+    raise ValueError(f"MI355X_OPTIM={kind}: expected sgd or lars (momentum), "
+                     "adamw or lamb (adaptive)")
 
 
 def schedule_from_env(lr: float, steps_per_epoch: int, epochs: int):
@@ -508,8 +640,12 @@ def ema_from_env():
 def describe(opt) -> str:
     """One line for a training log: the optimizer and what it was built
     with."""
-    s = (f"{type(opt).__name__} lr={float(opt.lr):g} "
-         f"momentum={opt.momentum:g} weight_decay={opt.weight_decay:g}")
+    s = f"{type(opt).__name__} lr={float(opt.lr):g} "
+    if isinstance(opt, AdamW):
+        s += f"betas=({opt.betas[0]:g}, {opt.betas[1]:g}) eps={opt.eps:g}"
+    else:
+        s += f"momentum={opt.momentum:g}"
+    s += f" weight_decay={opt.weight_decay:g}"
     if isinstance(opt, LARS):
         s += f" trust_coefficient={opt.trust_coefficient:g}"
     # under a schedule lr above is the next step's (float() of it syncs)
