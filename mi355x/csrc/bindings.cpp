@@ -98,6 +98,10 @@ std::vector<at::Tensor> se_bwd(at::Tensor x, at::Tensor dy, at::Tensor mask,
 std::vector<at::Tensor> se_wgrad(at::Tensor s, at::Tensor z, at::Tensor dl,
                                  at::Tensor dz);
 
+std::vector<at::Tensor> attn_fwd(at::Tensor qkv, double scale);
+at::Tensor attn_bwd(at::Tensor qkv, at::Tensor o, at::Tensor lse,
+                    at::Tensor dout, double scale);
+
 std::vector<at::Tensor> maxpool_fwd(at::Tensor x, long kernel, long stride,
                                     long pad);
 at::Tensor maxpool_bwd(at::Tensor dy, at::Tensor idx, long H, long W,
@@ -172,6 +176,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("se_fwd", &se_fwd);
   m.def("se_bwd", &se_bwd);
   m.def("se_wgrad", &se_wgrad);
+  m.def("attn_fwd", &attn_fwd);
+  m.def("attn_bwd", &attn_bwd);
   m.def("maxpool_fwd", &maxpool_fwd);
   m.def("maxpool_bwd", &maxpool_bwd);
   m.def("global_avg_pool", &global_avg_pool);

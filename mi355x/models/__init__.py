@@ -1,6 +1,7 @@
 from .mobilenet import MobileNet, mobilenet  # noqa: F401
 from .net import Net  # noqa: F401
 from .resnet import ResNet, resnet18, resnet50  # noqa: F401
+from .vit import ViT, vit_cifar  # noqa: F401
 
 
 def build_model(name: str, num_classes: int = 10):
@@ -29,4 +30,6 @@ def build_model(name: str, num_classes: int = 10):
         return resnet50(num_classes=num_classes, stem="cifar", se=16)
     if name == "mobilenet":
         return mobilenet(num_classes=num_classes)
+    if name == "vit_cifar":
+        return vit_cifar(num_classes=num_classes)
     raise ValueError(f"unknown model {name!r}")

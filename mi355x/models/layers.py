@@ -153,6 +153,47 @@ class GroupNorm(nn.Module):
                               residual, self.act, self.eps)
 
 
+class LayerNorm(nn.Module):
+    """LayerNorm over the last dimension: ops.group_norm with one group on
+    the [M,1,1,dim] view (every row is a "sample" of dim channels), so the
+    domain is group_norm's: dim a power of two (and at least 8). weight
+    and bias are [dim]; a state_dict interchanges with torch.nn.LayerNorm."""
+
+    def __init__(self, dim, eps=1e-5):
+        super().__init__()
+        if dim < 8 or dim & (dim - 1):
+            raise ValueError(f"LayerNorm: dim={dim} is not a power of two "
+                             "of at least 8")
+        self.dim, self.eps = dim, eps
+        self.weight = nn.Parameter(torch.ones(dim))
+        self.bias = nn.Parameter(torch.zeros(dim))
+
+    def forward(self, x):
+        y = ops.group_norm(x.reshape(-1, 1, 1, self.dim), 1, self.weight,
+                           self.bias, None, None, self.eps)
+        return y.reshape(x.shape)
+
+
+class MultiHeadAttention(nn.Module):
+    """Self-attention over [B,S,dim]: qkv projection, ops.attention on its
+    packed output (no permute or split in between), output projection."""
+
+    def __init__(self, dim, num_heads):
+        super().__init__()
+        if num_heads < 1 or dim % num_heads:
+            raise ValueError(f"MultiHeadAttention: num_heads={num_heads} "
+                             f"does not divide dim={dim}")
+        self.dim, self.num_heads = dim, num_heads
+        self.qkv = Linear(dim, 3 * dim)
+        self.proj = Linear(dim, dim)
+
+    def forward(self, x):
+        B, S, D = x.shape
+        qkv = self.qkv(x.reshape(B * S, D)).reshape(B, S, 3 * D)
+        o = ops.attention(qkv, self.num_heads)
+        return self.proj(o.reshape(B * S, D)).reshape(B, S, D)
+
+
 class SqueezeExcite(nn.Module):
     """Squeeze-and-excitation gate (Hu et al. 2018) over NHWC with optional
     fused residual-add + ReLU epilogue (ops.squeeze_excite lists the

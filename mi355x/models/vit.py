@@ -1,0 +1,78 @@
+"""Vision Transformer (Dosovitskiy et al. 2021) for 32-pixel input on the
+mi355x op layer.
+
+Patches are cut from the NHWC tensor by a view and one permute copy and
+embedded by a Linear(patch*patch*3, dim); a learned position embedding
+[S, dim] is added. Blocks are pre-norm:
+
+    x = x + proj(attention(qkv(LN(x))))
+    x = x + fc2(relu(fc1(LN(x))))
+
+This is a ReLU-MLP ViT: the library's linear epilogue fuses ReLU and has no
+GELU. The head is a final LayerNorm, the mean over the token grid
+(ops.global_avg_pool on [B,h,w,dim]) and a Linear; there is no class token,
+so the sequence length stays (image / patch) ** 2: 64 at the defaults.
+
+The residual adds and the position add are plain tensor adds; LayerNorm is
+ops.group_norm with one group (dim must be a power of two); attention is
+the fused kernel of csrc/attn.hip (dim / heads must be 32 or 64, at most
+256 tokens).
+"""
+
+from __future__ import annotations
+
+import torch
+from torch import nn
+
+from .layers import LayerNorm, Linear, MultiHeadAttention, to_model_layout
+from mi355x import ops
+
+
+class Block(nn.Module):
+    def __init__(self, dim, heads, mlp_dim):
+        super().__init__()
+        self.norm1 = LayerNorm(dim)
+        self.attn = MultiHeadAttention(dim, heads)
+        self.norm2 = LayerNorm(dim)
+        self.fc1 = Linear(dim, mlp_dim, act="relu")
+        self.fc2 = Linear(mlp_dim, dim)
+
+    def forward(self, x):
+        B, S, D = x.shape
+        x = x + self.attn(self.norm1(x))
+        h = self.fc2(self.fc1(self.norm2(x).reshape(B * S, D)))
+        return x + h.reshape(B, S, D)
+
+
+class ViT(nn.Module):
+    def __init__(self, image=32, patch=4, dim=256, depth=6, heads=4,
+                 mlp_dim=1024, num_classes=10):
+        super().__init__()
+        if image % patch:
+            raise ValueError(f"ViT: patch={patch} does not divide "
+                             f"image={image}")
+        self.patch, self.grid, self.dim = patch, image // patch, dim
+        self.embed = Linear(patch * patch * 3, dim)
+        self.pos = nn.Parameter(torch.empty(self.grid ** 2, dim))
+        nn.init.trunc_normal_(self.pos, std=0.02)
+        self.blocks = nn.Sequential(*(Block(dim, heads, mlp_dim)
+                                      for _ in range(depth)))
+        self.norm = LayerNorm(dim)
+        self.fc = Linear(dim, num_classes)
+
+    def forward(self, x):
+        x = to_model_layout(x)  # NCHW -> NHWC, 16-bit on GPU
+        B, p, g = x.shape[0], self.patch, self.grid
+        if x.shape[1:] != (g * p, g * p, 3):
+            raise ValueError(f"ViT: input {tuple(x.shape[1:])} (HWC) is not "
+                             f"{(g * p, g * p, 3)}")
+        x = x.reshape(B, g, p, g, p, 3).permute(0, 1, 3, 2, 4, 5)
+        x = self.embed(x.reshape(B * g * g, p * p * 3))
+        x = x.reshape(B, g * g, self.dim) + self.pos.to(x.dtype)
+        x = self.norm(self.blocks(x))
+        x = ops.global_avg_pool(x.reshape(B, g, g, self.dim))
+        return self.fc(x)
+
+
+def vit_cifar(num_classes=10):
+    return ViT(num_classes=num_classes)

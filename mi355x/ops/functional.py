@@ -766,6 +766,87 @@ def squeeze_excite(x, w1, b1, w2, b2, residual=None, act=None):
 
 
 # ---------------------------------------------------------------------------
+# multi-head self-attention (fused, S <= 256)
+# ---------------------------------------------------------------------------
+
+
+def _check_attention(qkv, num_heads, scale):
+    """The attention domain (the same on both devices): every value outside
+    it is named in a ValueError. Returns (B, S, H, dh, scale)."""
+    H = num_heads
+    if not isinstance(H, int) or H < 1:
+        raise ValueError(f"attention: num_heads={H!r} must be a positive "
+                         "integer")
+    if qkv.dim() == 5:
+        if qkv.shape[2] != 3 or qkv.shape[3] != H:
+            raise ValueError(f"attention: qkv {tuple(qkv.shape)} must be "
+                             f"[B,S,3,{H},dh]")
+        dh = qkv.shape[4]
+    elif qkv.dim() == 3:
+        if qkv.shape[2] % (3 * H) != 0:
+            raise ValueError(f"attention: last dimension={qkv.shape[2]} is "
+                             f"not divisible by 3 * num_heads={3 * H}")
+        dh = qkv.shape[2] // (3 * H)
+    else:
+        raise ValueError(f"attention: qkv must be [B,S,3*D] or [B,S,3,H,dh], "
+                         f"got {qkv.dim()} dimensions")
+    B, S = qkv.shape[0], qkv.shape[1]
+    if dh not in (32, 64):
+        raise ValueError(f"attention: head width={dh} must be 32 or 64")
+    if not 1 <= S <= 256:
+        raise ValueError(f"attention: sequence length={S} must be in "
+                         "[1, 256]")
+    if B < 1:
+        raise ValueError(f"attention: batch={B} must be at least 1")
+    scale = dh ** -0.5 if scale is None else float(scale)
+    if not (0.0 < scale < float("inf")):
+        raise ValueError(f"attention: scale={scale} must be positive and "
+                         "finite")
+    return B, S, H, dh, scale
+
+
+class _AttnFn(torch.autograd.Function):
+    """Fused attention over the packed qkv [B,S,3,H,dh]: the two bindings
+    of csrc/attn.hip. Only o and the fp32 row log-sum-exp are kept."""
+
+    @staticmethod
+    def forward(ctx, qkv, scale):
+        if qkv.dtype not in (torch.bfloat16, torch.float16):
+            raise ValueError(f"attention: the GPU kernels take bfloat16 or "
+                             f"float16, got {qkv.dtype}")
+        qkv = qkv.contiguous()
+        o, lse = ext().attn_fwd(qkv, scale)
+        ctx.save_for_backward(qkv, o, lse)
+        ctx.scale = scale
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        qkv, o, lse = ctx.saved_tensors
+        return ext().attn_bwd(qkv, o, lse, do.contiguous(), ctx.scale), None
+
+
+def attention(qkv, num_heads, scale=None):
+    """Multi-head self-attention over the packed output of the qkv
+    projection, per (batch, head):
+
+        o = softmax(scale * q k^T) v,   q, k, v = qkv[:, :, 0/1/2, h, :]
+
+    qkv: [B,S,3*D] or [B,S,3,H,dh] with D = num_heads * dh; returns
+    [B,S,D]. scale defaults to dh ** -0.5. No mask, no dropout. Domain: dh
+    32 or 64, 1 <= S <= 256, scale positive; anything else raises
+    ValueError. GPU: the kernels of csrc/attn.hip on 16-bit input (never
+    eager torch); scores and probabilities stay on the chip."""
+    B, S, H, dh, scale = _check_attention(qkv, num_heads, scale)
+    qkv = qkv.reshape(B, S, 3, H, dh)
+    if qkv.is_cuda:
+        return _AttnFn.apply(qkv, scale)
+    q, k, v = (qkv[:, :, i].permute(0, 2, 1, 3).float() for i in range(3))
+    p = torch.softmax(scale * (q @ k.transpose(-1, -2)), dim=-1)
+    return (p @ v).permute(0, 2, 1, 3).reshape(B, S, H * dh)
+
+
+# ---------------------------------------------------------------------------
 # pooling
 # ---------------------------------------------------------------------------
 

@@ -28,6 +28,7 @@ SRC = [
     "mi355x/csrc/bn.hip",
     "mi355x/csrc/gn.hip",
     "mi355x/csrc/se.hip",
+    "mi355x/csrc/attn.hip",
     "mi355x/csrc/pool.hip",
     "mi355x/csrc/gemm.hip",
     "mi355x/csrc/gemm_mfma.hip",
