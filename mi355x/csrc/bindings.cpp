@@ -87,6 +87,12 @@ std::vector<at::Tensor> gn_bwd(at::Tensor x, at::Tensor dy, at::Tensor mean,
                                at::Tensor mask, long G, bool want_dres,
                                long path);
 
+std::vector<at::Tensor> ln_fwd(at::Tensor x, at::Tensor r, at::Tensor gamma,
+                               at::Tensor beta, double eps, long nv);
+std::vector<at::Tensor> ln_bwd(at::Tensor s, at::Tensor dy, at::Tensor ds,
+                               at::Tensor mean, at::Tensor rstd,
+                               at::Tensor gamma, long nv);
+
 std::vector<at::Tensor> se_fwd(at::Tensor x, at::Tensor w1, at::Tensor b1,
                                at::Tensor w2t, at::Tensor b2, at::Tensor res,
                                long act, bool want_side, long path,
@@ -173,6 +179,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bn_bwd_dx", &bn_bwd_dx);
   m.def("gn_fwd", &gn_fwd);
   m.def("gn_bwd", &gn_bwd);
+  m.def("ln_fwd", &ln_fwd);
+  m.def("ln_bwd", &ln_bwd);
   m.def("se_fwd", &se_fwd);
   m.def("se_bwd", &se_bwd);
   m.def("se_wgrad", &se_wgrad);

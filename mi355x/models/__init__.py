@@ -1,7 +1,7 @@
 from .mobilenet import MobileNet, mobilenet  # noqa: F401
 from .net import Net  # noqa: F401
 from .resnet import ResNet, resnet18, resnet50  # noqa: F401
-from .vit import ViT, vit_cifar  # noqa: F401
+from .vit import ViT, vit_cifar, vit_cifar_s  # noqa: F401
 
 
 def build_model(name: str, num_classes: int = 10):
@@ -32,4 +32,6 @@ def build_model(name: str, num_classes: int = 10):
         return mobilenet(num_classes=num_classes)
     if name == "vit_cifar":
         return vit_cifar(num_classes=num_classes)
+    if name == "vit_cifar_s":
+        return vit_cifar_s(num_classes=num_classes)
     raise ValueError(f"unknown model {name!r}")

@@ -154,24 +154,37 @@ class GroupNorm(nn.Module):
 
 
 class LayerNorm(nn.Module):
-    """LayerNorm over the last dimension: ops.group_norm with one group on
-    the [M,1,1,dim] view (every row is a "sample" of dim channels), so the
-    domain is group_norm's: dim a power of two (and at least 8). weight
-    and bias are [dim]; a state_dict interchanges with torch.nn.LayerNorm."""
+    """LayerNorm over the last dimension, with the residual add in front of
+    it fused when a residual is given: forward(x) -> y, forward(x, residual)
+    -> (s, y) with s = x + residual and y = LN(s).
+
+    dim is a multiple of 32 up to 4096 (ops.layer_norm, csrc/ln.hip) or a
+    power of two of at least 8; the powers of two outside the op's domain
+    (8, 16, above 4096) take ops.group_norm with one group on the
+    [M,1,1,dim] view, every row a "sample" of dim channels. weight and bias
+    are [dim]; a state_dict interchanges with torch.nn.LayerNorm."""
 
     def __init__(self, dim, eps=1e-5):
         super().__init__()
-        if dim < 8 or dim & (dim - 1):
-            raise ValueError(f"LayerNorm: dim={dim} is not a power of two "
-                             "of at least 8")
+        from mi355x.ops.functional import layer_norm_serves
+
+        self._row_op = layer_norm_serves(dim)
+        if not self._row_op and (dim < 8 or dim & (dim - 1)):
+            raise ValueError(f"LayerNorm: dim={dim} is neither a multiple of "
+                             "32 up to 4096 nor a power of two of at least 8")
         self.dim, self.eps = dim, eps
         self.weight = nn.Parameter(torch.ones(dim))
         self.bias = nn.Parameter(torch.zeros(dim))
 
-    def forward(self, x):
-        y = ops.group_norm(x.reshape(-1, 1, 1, self.dim), 1, self.weight,
+    def forward(self, x, residual=None):
+        if self._row_op:
+            return ops.layer_norm(x, self.weight, self.bias, residual,
+                                  self.eps)
+        s = x if residual is None else x + residual
+        y = ops.group_norm(s.reshape(-1, 1, 1, self.dim), 1, self.weight,
                            self.bias, None, None, self.eps)
-        return y.reshape(x.shape)
+        y = y.reshape(s.shape)
+        return y if residual is None else (s, y)
 
 
 class MultiHeadAttention(nn.Module):

@@ -13,10 +13,18 @@ GELU. The head is a final LayerNorm, the mean over the token grid
 (ops.global_avg_pool on [B,h,w,dim]) and a Linear; there is no class token,
 so the sequence length stays (image / patch) ** 2: 64 at the defaults.
 
-The residual adds and the position add are plain tensor adds; LayerNorm is
-ops.group_norm with one group (dim must be a power of two); attention is
-the fused kernel of csrc/attn.hip (dim / heads must be 32 or 64, at most
-256 tokens).
+The forward computes exactly that, but every residual add is fused into the
+LayerNorm that follows it (ops.layer_norm with a residual returns the sum
+and its norm from one pass, csrc/ln.hip): a block receives the stream and
+the previous block's MLP output, norm2 adds the attention output, the next
+block's norm1 adds the MLP output and the final LayerNorm adds the last
+one. That is 2*depth + 1 LayerNorm launches, 2*depth of them with an add;
+only the position add is a plain tensor add. dim is a multiple of 32 up to
+4096; attention is the fused kernel of csrc/attn.hip (dim / heads must be
+32 or 64, at most 256 tokens).
+
+vit_cifar is dim 256, 4 heads, MLP 1024; vit_cifar_s is dim 384, 6 heads,
+MLP 1536. Both have depth 6 and 4-pixel patches.
 """
 
 from __future__ import annotations
@@ -37,11 +45,18 @@ class Block(nn.Module):
         self.fc1 = Linear(dim, mlp_dim, act="relu")
         self.fc2 = Linear(mlp_dim, dim)
 
-    def forward(self, x):
+    def forward(self, x, h=None):
+        """x: the stream; h: the previous block's MLP output, not yet added
+        (None in front of the first block). Returns the pair for the next
+        block."""
         B, S, D = x.shape
-        x = x + self.attn(self.norm1(x))
-        h = self.fc2(self.fc1(self.norm2(x).reshape(B * S, D)))
-        return x + h.reshape(B, S, D)
+        if h is None:
+            y = self.norm1(x)
+        else:
+            x, y = self.norm1(x, h)
+        x, y = self.norm2(x, self.attn(y))
+        h = self.fc2(self.fc1(y.reshape(B * S, D)))
+        return x, h.reshape(B, S, D)
 
 
 class ViT(nn.Module):
@@ -69,10 +84,17 @@ class ViT(nn.Module):
         x = x.reshape(B, g, p, g, p, 3).permute(0, 1, 3, 2, 4, 5)
         x = self.embed(x.reshape(B * g * g, p * p * 3))
         x = x.reshape(B, g * g, self.dim) + self.pos.to(x.dtype)
-        x = self.norm(self.blocks(x))
+        h = None
+        for block in self.blocks:
+            x, h = block(x, h)
+        x = self.norm(x) if h is None else self.norm(x, h)[1]
         x = ops.global_avg_pool(x.reshape(B, g, g, self.dim))
         return self.fc(x)
 
 
 def vit_cifar(num_classes=10):
     return ViT(num_classes=num_classes)
+
+
+def vit_cifar_s(num_classes=10):
+    return ViT(dim=384, heads=6, mlp_dim=1536, num_classes=num_classes)

@@ -654,6 +654,102 @@ def group_norm(x, num_groups, gamma, beta, residual=None, act=None,
 
 
 # ---------------------------------------------------------------------------
+# layer norm (+ the residual add in front of it, fused)
+# ---------------------------------------------------------------------------
+
+
+def layer_norm_serves(dim) -> bool:
+    """Whether `dim` is in ops.layer_norm's domain."""
+    return dim % 32 == 0 and 32 <= dim <= 4096
+
+
+def _check_layer_norm(x, gamma, beta, residual):
+    """The layer_norm domain (the same on both devices): every value outside
+    it is named in a ValueError."""
+    if x.dim() < 1 or x.numel() == 0:
+        raise ValueError(f"layer_norm: x {tuple(x.shape)} must be a non-empty "
+                         "[..., D]")
+    D = x.shape[-1]
+    if not layer_norm_serves(D):
+        raise ValueError(f"layer_norm: D={D} is not a multiple of 32 in "
+                         "[32, 4096]")
+    if gamma.shape != (D,) or beta.shape != (D,):
+        raise ValueError(f"layer_norm: gamma and beta must be [{D}], got "
+                         f"{tuple(gamma.shape)} and {tuple(beta.shape)}")
+    if residual is not None and (residual.shape != x.shape
+                                 or residual.dtype != x.dtype):
+        raise ValueError(f"layer_norm: residual {tuple(residual.shape)} "
+                         f"{residual.dtype} must match x {tuple(x.shape)} "
+                         f"{x.dtype}")
+
+
+class _LNFn(torch.autograd.Function):
+    """LayerNorm over the last dimension with the residual add in front of
+    it fused: the two bindings of csrc/ln.hip. Returns y, or (s, y) with a
+    residual. nv (0 = the kernel's rule) fixes the vectors per lane;
+    ops.layer_norm always passes 0."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, residual, eps, nv=0):
+        if x.dtype not in (torch.bfloat16, torch.float16):
+            raise ValueError(f"layer_norm: the GPU kernels take bfloat16 or "
+                             f"float16, got {x.dtype}")
+        D = x.shape[-1]
+        x2 = x.contiguous().view(-1, D)
+        res = (residual.contiguous().view(-1, D) if residual is not None
+               else torch.empty(0, device=x.device, dtype=x.dtype))
+        g32 = gamma.detach().float().contiguous()
+        y, s, mean, rstd = ext().ln_fwd(
+            x2, res, g32, beta.detach().float().contiguous(), eps, nv)
+        ctx.set_materialize_grads(False)
+        ctx.conf = (residual is not None, nv, x.shape)
+        if any(ctx.needs_input_grad):
+            ctx.save_for_backward(s if residual is not None else x2, mean,
+                                  rstd, g32)
+        if residual is None:
+            return y.view(x.shape)
+        return s.view(x.shape), y.view(x.shape)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        has_res, nv, shape = ctx.conf
+        ds, dy = grads if has_res else (None, grads[0])
+        if dy is None:  # y unused: the add alone
+            return ds, None, None, ds, None, None
+        s, mean, rstd, g32 = ctx.saved_tensors
+        D = shape[-1]
+        ds2 = (ds.contiguous().view(-1, D) if ds is not None
+               else torch.empty(0, device=s.device, dtype=s.dtype))
+        d, dgb = ext().ln_bwd(s, dy.contiguous().view(-1, D), ds2, mean,
+                              rstd, g32, nv)
+        d = d.view(shape)
+        return d, dgb[0], dgb[1], d if has_res else None, None, None
+
+
+def layer_norm(x, gamma, beta, residual=None, eps=1e-5):
+    """LayerNorm (Ba et al. 2016) over the last dimension of x [..., D],
+    biased variance, with the pre-norm residual add fused in:
+
+        y = (x - mean) * rstd * gamma + beta                  -> y
+        s = x + residual;  y = LN(s)                          -> (s, y)
+
+    On the GPU s is rounded once to the 16-bit type and y is the LayerNorm
+    of that stored s; both gradients of the add are one tensor.
+
+    Domain: D a multiple of 32 in [32, 4096], gamma and beta [D], residual
+    of x's shape and dtype; anything else raises ValueError. GPU: the
+    kernels of csrc/ln.hip on 16-bit input (never eager torch); under
+    torch.no_grad() nothing is saved."""
+    _check_layer_norm(x, gamma, beta, residual)
+    if x.is_cuda:
+        return _LNFn.apply(x, gamma, beta, residual, float(eps))
+    if residual is None:
+        return F.layer_norm(x.float(), x.shape[-1:], gamma, beta, eps)
+    s = x.float() + residual
+    return s, F.layer_norm(s, s.shape[-1:], gamma, beta, eps)
+
+
+# ---------------------------------------------------------------------------
 # squeeze-and-excitation (+ residual add + relu, fused)
 # ---------------------------------------------------------------------------
 

@@ -27,6 +27,7 @@ SRC = [
     "mi355x/csrc/wcast.hip",
     "mi355x/csrc/bn.hip",
     "mi355x/csrc/gn.hip",
+    "mi355x/csrc/ln.hip",
     "mi355x/csrc/se.hip",
     "mi355x/csrc/attn.hip",
     "mi355x/csrc/pool.hip",
