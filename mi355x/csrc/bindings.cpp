@@ -120,6 +120,13 @@ at::Tensor linear_wgrad(at::Tensor x, at::Tensor dy);
 at::Tensor gemm_nt_mfma(at::Tensor A, at::Tensor B, at::Tensor bias, long act,
                         bool out32);
 
+std::vector<at::Tensor> mlp_fwd(at::Tensor x, at::Tensor w1, at::Tensor b1,
+                                at::Tensor w2, at::Tensor b2, long act,
+                                long bk);
+std::vector<at::Tensor> mlp_bwd(at::Tensor dy, at::Tensor x, at::Tensor h,
+                                at::Tensor z, at::Tensor w1t, at::Tensor w2t,
+                                long act, bool want_dx, long bk);
+
 std::vector<at::Tensor> cross_entropy_fwd(at::Tensor logits,
                                           at::Tensor target);
 at::Tensor cross_entropy_bwd(at::Tensor logits, at::Tensor target,
@@ -193,6 +200,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("linear_dgrad", &linear_dgrad);
   m.def("linear_wgrad", &linear_wgrad);
   m.def("gemm_nt_mfma", &gemm_nt_mfma);
+  m.def("mlp_fwd", &mlp_fwd);
+  m.def("mlp_bwd", &mlp_bwd);
   m.def("cross_entropy_fwd", &cross_entropy_fwd);
   m.def("cross_entropy_bwd", &cross_entropy_bwd);
   m.def("cross_entropy_soft_fwd", &cross_entropy_soft_fwd);

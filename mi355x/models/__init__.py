@@ -34,4 +34,8 @@ def build_model(name: str, num_classes: int = 10):
         return vit_cifar(num_classes=num_classes)
     if name == "vit_cifar_s":
         return vit_cifar_s(num_classes=num_classes)
+    if name == "vit_cifar_gelu":
+        return vit_cifar(num_classes=num_classes, mlp_act="gelu")
+    if name == "vit_cifar_s_gelu":
+        return vit_cifar_s(num_classes=num_classes, mlp_act="gelu")
     raise ValueError(f"unknown model {name!r}")

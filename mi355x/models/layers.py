@@ -228,6 +228,25 @@ class SqueezeExcite(nn.Module):
                                   self.act)
 
 
+class MLP(nn.Module):
+    """The transformer MLP on [M, dim]: fc2(act(fc1(x))) with act "gelu"
+    (exact) or "relu" (ops.mlp lists the domain). fc1 and fc2 only hold the
+    parameters: the whole block is one op."""
+
+    def __init__(self, dim, hidden, act="gelu"):
+        super().__init__()
+        if act not in ("gelu", "relu"):
+            raise ValueError(f"MLP: act={act!r} is neither 'gelu' nor "
+                             "'relu'")
+        self.act = act
+        self.fc1 = Linear(dim, hidden)
+        self.fc2 = Linear(hidden, dim)
+
+    def forward(self, x):
+        return ops.mlp(x, self.fc1.weight, self.fc1.bias, self.fc2.weight,
+                       self.fc2.bias, self.act)
+
+
 def conv_gn_tap(conv: "Conv2d", gn: "GroupNorm", x):
     """conv -> GroupNorm returning (out, tap): conv_bn_tap without the
     BN-only statistics fusion. The block's shortcut consumes `tap`, so the

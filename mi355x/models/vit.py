@@ -6,12 +6,16 @@ embedded by a Linear(patch*patch*3, dim); a learned position embedding
 [S, dim] is added. Blocks are pre-norm:
 
     x = x + proj(attention(qkv(LN(x))))
-    x = x + fc2(relu(fc1(LN(x))))
+    x = x + fc2(act(fc1(LN(x))))
 
-This is a ReLU-MLP ViT: the library's linear epilogue fuses ReLU and has no
-GELU. The head is a final LayerNorm, the mean over the token grid
-(ops.global_avg_pool on [B,h,w,dim]) and a Linear; there is no class token,
-so the sequence length stays (image / patch) ** 2: 64 at the defaults.
+mlp_act selects the MLP. "relu" (the default, vit_cifar and vit_cifar_s) runs
+fc1 and fc2 as two ops.linear calls with ReLU fused into fc1's epilogue.
+"gelu" (vit_cifar_gelu, vit_cifar_s_gelu) runs the pair as one ops.mlp with
+the exact GELU (csrc/mlp.hip); the parameters are the same fc1 and fc2, so a
+checkpoint loads into either. The head is a final LayerNorm, the mean over
+the token grid (ops.global_avg_pool on [B,h,w,dim]) and a Linear; there is no
+class token, so the sequence length stays (image / patch) ** 2: 64 at the
+defaults.
 
 The forward computes exactly that, but every residual add is fused into the
 LayerNorm that follows it (ops.layer_norm with a residual returns the sum
@@ -24,7 +28,8 @@ only the position add is a plain tensor add. dim is a multiple of 32 up to
 32 or 64, at most 256 tokens).
 
 vit_cifar is dim 256, 4 heads, MLP 1024; vit_cifar_s is dim 384, 6 heads,
-MLP 1536. Both have depth 6 and 4-pixel patches.
+MLP 1536. Both have depth 6 and 4-pixel patches; the _gelu names are the same
+shapes with mlp_act="gelu".
 """
 
 from __future__ import annotations
@@ -37,12 +42,17 @@ from mi355x import ops
 
 
 class Block(nn.Module):
-    def __init__(self, dim, heads, mlp_dim):
+    def __init__(self, dim, heads, mlp_dim, mlp_act="relu"):
         super().__init__()
+        if mlp_act not in ("relu", "gelu"):
+            raise ValueError(f"ViT: mlp_act={mlp_act!r} is neither 'relu' "
+                             "nor 'gelu'")
+        self.mlp_act = mlp_act
         self.norm1 = LayerNorm(dim)
         self.attn = MultiHeadAttention(dim, heads)
         self.norm2 = LayerNorm(dim)
-        self.fc1 = Linear(dim, mlp_dim, act="relu")
+        self.fc1 = Linear(dim, mlp_dim,
+                          act="relu" if mlp_act == "relu" else None)
         self.fc2 = Linear(mlp_dim, dim)
 
     def forward(self, x, h=None):
@@ -55,13 +65,17 @@ class Block(nn.Module):
         else:
             x, y = self.norm1(x, h)
         x, y = self.norm2(x, self.attn(y))
-        h = self.fc2(self.fc1(y.reshape(B * S, D)))
+        if self.mlp_act == "relu":
+            h = self.fc2(self.fc1(y.reshape(B * S, D)))
+        else:
+            h = ops.mlp(y.reshape(B * S, D), self.fc1.weight, self.fc1.bias,
+                        self.fc2.weight, self.fc2.bias, self.mlp_act)
         return x, h.reshape(B, S, D)
 
 
 class ViT(nn.Module):
     def __init__(self, image=32, patch=4, dim=256, depth=6, heads=4,
-                 mlp_dim=1024, num_classes=10):
+                 mlp_dim=1024, num_classes=10, mlp_act="relu"):
         super().__init__()
         if image % patch:
             raise ValueError(f"ViT: patch={patch} does not divide "
@@ -70,7 +84,7 @@ class ViT(nn.Module):
         self.embed = Linear(patch * patch * 3, dim)
         self.pos = nn.Parameter(torch.empty(self.grid ** 2, dim))
         nn.init.trunc_normal_(self.pos, std=0.02)
-        self.blocks = nn.Sequential(*(Block(dim, heads, mlp_dim)
+        self.blocks = nn.Sequential(*(Block(dim, heads, mlp_dim, mlp_act)
                                       for _ in range(depth)))
         self.norm = LayerNorm(dim)
         self.fc = Linear(dim, num_classes)
@@ -92,9 +106,10 @@ class ViT(nn.Module):
         return self.fc(x)
 
 
-def vit_cifar(num_classes=10):
-    return ViT(num_classes=num_classes)
+def vit_cifar(num_classes=10, mlp_act="relu"):
+    return ViT(num_classes=num_classes, mlp_act=mlp_act)
 
 
-def vit_cifar_s(num_classes=10):
-    return ViT(dim=384, heads=6, mlp_dim=1536, num_classes=num_classes)
+def vit_cifar_s(num_classes=10, mlp_act="relu"):
+    return ViT(dim=384, heads=6, mlp_dim=1536, num_classes=num_classes,
+               mlp_act=mlp_act)

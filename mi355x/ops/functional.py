@@ -469,6 +469,89 @@ def linear(x, weight, bias=None, act=None):
 
 
 # ---------------------------------------------------------------------------
+# transformer MLP (two GEMMs and the activation between them, fused)
+# ---------------------------------------------------------------------------
+
+_MLP_ACTS = {"relu": _ACT_RELU, "gelu": 2}
+
+
+def _check_mlp(x, w1, b1, w2, b2, act):
+    """The mlp domain (the same on both devices): every value outside it is
+    named in a ValueError."""
+    if act not in _MLP_ACTS:
+        raise ValueError(f"mlp: act={act!r} is neither 'gelu' nor 'relu'")
+    if x.dim() != 2 or x.shape[0] < 1:
+        raise ValueError(f"mlp: x must be a non-empty [M, D], got "
+                         f"{tuple(x.shape)}")
+    D = x.shape[1]
+    if w1.dim() != 2 or w1.shape[1] != D:
+        raise ValueError(f"mlp: w1 must be [F, {D}], got {tuple(w1.shape)}")
+    F_ = w1.shape[0]
+    for name, v in (("D", D), ("F", F_)):
+        if v < 8 or v % 8:
+            raise ValueError(f"mlp: {name}={v} is not a multiple of 8 of at "
+                             "least 8")
+    for name, t, shape in (("b1", b1, (F_,)), ("w2", w2, (D, F_)),
+                           ("b2", b2, (D,))):
+        if t is None:
+            raise ValueError(f"mlp: {name}=None; both biases are required")
+        if tuple(t.shape) != shape:
+            raise ValueError(f"mlp: {name} must be {list(shape)}, got "
+                             f"{tuple(t.shape)}")
+
+
+class _MLPFn(torch.autograd.Function):
+    """The bindings of csrc/mlp.hip: two GEMM launches forward, four plus
+    the folds backward. bk (0 = the kernel's rule) fixes the NT kernel's
+    k-slice; ops.mlp always passes 0."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2, act, bk=0):
+        x = x.contiguous()
+        y, h, z = ext().mlp_fwd(
+            x, _w16_linear(w1, x.dtype), b1.detach().float(),
+            _w16_linear(w2, x.dtype), b2.detach().float(), act, bk)
+        ctx.save_for_backward(x, h, z)
+        ctx.weight_refs = (w1, w2)  # for the cached dgrad transposes
+        ctx.conf = (act, bk)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, h, z = ctx.saved_tensors
+        w1, w2 = ctx.weight_refs
+        act, bk = ctx.conf
+        dx, dw1, db1, dw2, db2 = ext().mlp_bwd(
+            dy.contiguous(), x, h, z, _w16_linear_t(w1, dy.dtype),
+            _w16_linear_t(w2, dy.dtype), act, ctx.needs_input_grad[0], bk)
+        return (dx if ctx.needs_input_grad[0] else None, dw1, db1, dw2, db2,
+                None, None)
+
+
+def mlp(x, w1, b1, w2, b2, act="gelu"):
+    """The transformer MLP on x [M, D]:
+
+        z = x w1^T + b1;   h = act(z);   y = h w2^T + b2
+
+    w1 [F,D], b1 [F], w2 [D,F], b2 [D] are fp32 parameters; act is "gelu"
+    (the exact 0.5 z (1 + erf(z / sqrt 2)), torch.nn.GELU's default) or
+    "relu". Domain: M >= 1, D and F multiples of 8 of at least 8, both
+    biases; anything else raises ValueError. GPU, 16-bit x: the kernels of
+    csrc/mlp.hip at every M (never eager torch, never ops.linear's GEMM);
+    h, and z for GELU, are rounded to x's dtype and kept for the backward,
+    whose activation derivative, bias gradients and weight-gradient
+    transposes all happen inside the four GEMMs. CPU, or another dtype: the
+    torch composition in x's dtype."""
+    _check_mlp(x, w1, b1, w2, b2, act)
+    if x.is_cuda and x.dtype in (torch.bfloat16, torch.float16):
+        return _MLPFn.apply(x, w1, b1, w2, b2, _MLP_ACTS[act])
+    dt = x.dtype
+    z = F.linear(x, w1.to(dt), b1.to(dt))
+    h = F.gelu(z) if act == "gelu" else F.relu(z)
+    return F.linear(h, w2.to(dt), b2.to(dt))
+
+
+# ---------------------------------------------------------------------------
 # batch norm (+ residual add + relu, fused)
 # ---------------------------------------------------------------------------
 

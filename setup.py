@@ -33,6 +33,7 @@ SRC = [
     "mi355x/csrc/pool.hip",
     "mi355x/csrc/gemm.hip",
     "mi355x/csrc/gemm_mfma.hip",
+    "mi355x/csrc/mlp.hip",
     "mi355x/csrc/stem_mfma.hip",
     "mi355x/csrc/loss.hip",
     "mi355x/csrc/meter.hip",
