@@ -22,13 +22,14 @@
 //
 //   kFused    AdamW: reads g w m v (e), writes m v w (e)        4 + 3 floats
 //   kMoments  LAMB 1: reads g w m v, writes m v; u stays in registers and
-//             w^2, u^2 go per tile into the slab (lanes, wave butterfly,
-//             4 LDS slots: one fixed order)                     4 + 2
+//             w^2, u^2 go per tile into the slab (lanes, then
+//             block_sum256 of reduce.h: one fixed order)        4 + 2
 //   kApply    LAMB 2: reads w m v (e), recomputes u from the stored moments
 //             with the same operations, writes w (e)            3 + 1
 //
 // Between the LAMB passes one block adds each tensor's tiles in tile order in
-// double and writes {||w_s||, ||u_s||, trust_s} into the plan's stats. No
+// double (combine_tiles, tile_plan.h, shared with lars_finalise_kernel) and
+// writes {||w_s||, ||u_s||, trust_s} into the plan's stats. No
 // float atomics, no last-block ticket: two runs, and two ranks that hold the
 // same gradient, give the same bits for any grid.
 #include "common.h"
@@ -132,14 +133,13 @@ __global__ __launch_bounds__(256) void adam_tiles_kernel(
     float* __restrict__ slab_u) {
   static_assert(!(kEma && kPass == kMoments), "the moments pass writes no w");
   if (reinterpret_cast<const int*>(st)[kNonFinite] != 0) return;  // skipped: no write
-  __shared__ float lw[4], lu[4];
   const AdamCoef c = adam_coef(clock, b1, b2, eps);
   const float lr = lr_dev ? *lr_dev : lr_host;
   TileCoef qc;
   qc.eff = guard_coef(st, gscale_host, max_norm).eff;
   qc.omd = 0.f;
   if constexpr (kEma) qc.omd = clock[kClkEmaOmd];
-  const int tid = threadIdx.x, wave = tid >> 6;
+  const int tid = threadIdx.x;
   for (int t = blockIdx.x; t < T; t += gridDim.x) {
     const Tile q = load_tile(table, t, n, S);
     float aw[4] = {0.f, 0.f, 0.f, 0.f}, au[4] = {0.f, 0.f, 0.f, 0.f};
@@ -214,90 +214,34 @@ __global__ __launch_bounds__(256) void adam_tiles_kernel(
     }
     if constexpr (kPass == kMoments) {
       // a tile that cannot be read adds 0 to its tensor's sums
-      float sw = (aw[0] + aw[1]) + (aw[2] + aw[3]);
-      float su = (au[0] + au[1]) + (au[2] + au[3]);
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) {
-        sw += __shfl_xor(sw, off, kWave);
-        su += __shfl_xor(su, off, kWave);
-      }
-      if ((tid & 63) == 0) {
-        lw[wave] = sw;
-        lu[wave] = su;
-      }
-      __syncthreads();
+      float sw = sum4(aw[0], aw[1], aw[2], aw[3]);
+      float su = sum4(au[0], au[1], au[2], au[3]);
+      block_sum256(sw, su);
       if (tid == 0) {
-        slab_w[t] = (lw[0] + lw[1]) + (lw[2] + lw[3]);
-        slab_u[t] = (lu[0] + lu[1]) + (lu[2] + lu[3]);
+        slab_w[t] = sw;
+        slab_u[t] = su;
       }
       __syncthreads();  // the LDS slots are reused by the next tile
     }
   }
 }
 
-// One block. Wave v owns tensors v, v+16, ...: lane l adds the tensor's
-// tiles l, l+64, ... in double, then a butterfly: one fixed order whatever
-// the grid of the moments pass. The guard state is only read: on a skipped
-// step the slab is stale and the stats stay what they were.
+// One block adds each tensor's tiles (combine_tiles, tile_plan.h): one fixed
+// order whatever the grid of the moments pass. The guard state is only read:
+// on a skipped step the slab is stale and the stats stay what they were.
 __global__ __launch_bounds__(kFinThreads) void lamb_finalise_kernel(
     const float* __restrict__ slab_w, const float* __restrict__ slab_u, int T,
     const int4v* __restrict__ tens, int S, const float* __restrict__ st,
     float* __restrict__ stats) {
   if (reinterpret_cast<const int*>(st)[kNonFinite] != 0) return;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  for (int s = wave; s < S; s += kFinWaves) {
-    const int4v e = tens[s];
-    const int t0 = max(e[0], 0), t1 = min(e[1], T);
-    double a = 0.0, b = 0.0;
-    for (int t = t0 + lane; t < t1; t += kWave) {
-      a += (double)slab_w[t];
-      b += (double)slab_u[t];
-    }
-    a = wave_sum(a);
-    b = wave_sum(b);
-    if (lane == 0) {
-      const float wn = (float)sqrt(a), un = (float)sqrt(b);
-      stats[3 * s + 0] = wn;
-      stats[3 * s + 1] = un;
-      stats[3 * s + 2] = (!e[2] && wn > 0.f && un > 0.f) ? wn / un : 1.f;
-    }
-  }
-}
-
-struct AdamHost {
-  long n;
-  PlanDims d;
-  const float* lr_ptr;
-  const float* clock;
-  float* e;
-};
-
-inline AdamHost check_adam(const at::Tensor& p, const at::Tensor& g,
-                           const at::Tensor& m, const at::Tensor& v,
-                           const at::Tensor& table, const at::Tensor& tens,
-                           const at::Tensor& state, const at::Tensor& stats,
-                           const at::Tensor& clock,
-                           const c10::optional<at::Tensor>& lr_dev,
-                           const c10::optional<at::Tensor>& ema, double b1,
-                           double b2, double eps) {
-  AdamHost h;
-  h.n = p.numel();
-  check_flat(p, "p", h.n);
-  check_flat(g, "g", h.n);
-  check_flat(m, "exp_avg", h.n);
-  check_flat(v, "exp_avg_sq", h.n);
-  check_f32(state, "state", kStateLen);
-  check_f32(clock, "clock", kClkLen);
-  TORCH_CHECK(clock.device() == p.device(),
-              "the clock must live on the parameters' device");
-  TORCH_CHECK(b1 >= 0.0 && b1 < 1.0, "beta1 must be in [0, 1), got ", b1);
-  TORCH_CHECK(b2 >= 0.0 && b2 < 1.0, "beta2 must be in [0, 1), got ", b2);
-  TORCH_CHECK(eps >= 0.0, "eps must be >= 0, got ", eps);
-  h.d = check_plan(table, tens, stats, h.n);
-  h.lr_ptr = lr_dev.has_value() ? check_dev_scalar(*lr_dev, p) : nullptr;
-  h.clock = clock.data_ptr<float>();
-  h.e = ema.has_value() ? check_ema(*ema, clock, p).e : nullptr;
-  return h;
+  combine_tiles(slab_w, slab_u, T, tens, S,
+                [&](int s, const int4v& e, double a, double b) {
+                  const float wn = (float)sqrt(a), un = (float)sqrt(b);
+                  stats[3 * s + 0] = wn;
+                  stats[3 * s + 1] = un;
+                  stats[3 * s + 2] =
+                      (!e[2] && wn > 0.f && un > 0.f) ? wn / un : 1.f;
+                });
 }
 
 }  // namespace
@@ -306,16 +250,58 @@ inline AdamHost check_adam(const at::Tensor& p, const at::Tensor& g,
 #pragma clang attribute pop
 #endif
 
-#define ADAM_TILES(PASS, EMA, SLAB_W, SLAB_U)                                \
-  hipLaunchKernelGGL(                                                        \
-      (adam_tiles_kernel<PASS, EMA>), dim3(h.d.grid), dim3(256), 0,          \
-      cur_stream(), p.data_ptr<float>(), g.data_ptr<float>(),                \
-      m.data_ptr<float>(), v.data_ptr<float>(), h.n,                         \
-      reinterpret_cast<const int4v*>(table.data_ptr<int>()), h.d.T,          \
-      reinterpret_cast<const int4v*>(tens.data_ptr<int>()), h.d.S,           \
-      state.data_ptr<float>(), stats.data_ptr<float>(), h.clock, h.lr_ptr,   \
-      (float)lr, b1, b2, (float)eps, (float)wd, (float)gscale,               \
-      (float)max_norm, h.e, SLAB_W, SLAB_U)
+// adam_step (slab == nullptr: one kFused pass) and lamb_step (kMoments, the
+// combine, kApply) take the same arguments through the same checks
+static void adaptive_step(const at::Tensor* slab, const at::Tensor& p,
+                          const at::Tensor& g, const at::Tensor& m,
+                          const at::Tensor& v, const at::Tensor& table,
+                          const at::Tensor& tens, const at::Tensor& state,
+                          const at::Tensor& stats, const at::Tensor& clock,
+                          const c10::optional<at::Tensor>& lr_dev, double lr,
+                          double b1, double b2, double eps, double wd,
+                          double gscale, double max_norm,
+                          const c10::optional<at::Tensor>& ema) {
+  const PlanDims d = check_plan(p, g, state, table, tens, stats);
+  check_flat(m, "exp_avg", p.numel());
+  check_flat(v, "exp_avg_sq", p.numel());
+  check_f32(clock, "clock", kClkLen);
+  TORCH_CHECK(clock.device() == p.device(),
+              "the clock must live on the parameters' device");
+  TORCH_CHECK(b1 >= 0.0 && b1 < 1.0, "beta1 must be in [0, 1), got ", b1);
+  TORCH_CHECK(b2 >= 0.0 && b2 < 1.0, "beta2 must be in [0, 1), got ", b2);
+  TORCH_CHECK(eps >= 0.0, "eps must be >= 0, got ", eps);
+  const float* lr_ptr = lr_dev.has_value() ? check_dev_scalar(*lr_dev, p)
+                                           : nullptr;
+  float* e = ema.has_value() ? check_ema(*ema, clock, p).e : nullptr;
+  if (slab) check_f32(*slab, "plan slab", 2L * d.T);
+  if (d.T == 0) return;
+  float* sw = slab ? slab->data_ptr<float>() : nullptr;
+  float* su = slab ? sw + d.T : nullptr;
+
+  auto tiles = [&](auto kPass) {
+    auto launch = [&](auto kEma) {
+      launch256(adam_tiles_kernel<kPass, kEma>, dim3(d.grid), 0,
+                p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(),
+                v.data_ptr<float>(), p.numel(), int4_rows(table), d.T,
+                int4_rows(tens), d.S, state.data_ptr<float>(),
+                stats.data_ptr<float>(), clock.data_ptr<float>(), lr_ptr, lr,
+                b1, b2, eps, wd, gscale, max_norm, e, sw, su);
+    };
+    if constexpr (kPass == kMoments)
+      launch(std::false_type{});  // writes no w, so no EMA variant
+    else
+      pick<true, false>(e != nullptr, launch);
+  };
+  if (!slab) {
+    tiles(std::integral_constant<int, kFused>{});
+    return;
+  }
+  tiles(std::integral_constant<int, kMoments>{});
+  hipLaunchKernelGGL(lamb_finalise_kernel, dim3(1), dim3(kFinThreads), 0,
+                     cur_stream(), sw, su, d.T, int4_rows(tens), d.S,
+                     state.data_ptr<float>(), stats.data_ptr<float>());
+  tiles(std::integral_constant<int, kApply>{});
+}
 
 void adam_step(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v,
                at::Tensor table, at::Tensor tens, at::Tensor state,
@@ -323,14 +309,8 @@ void adam_step(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v,
                c10::optional<at::Tensor> lr_dev, double lr, double b1,
                double b2, double eps, double wd, double gscale,
                double max_norm, c10::optional<at::Tensor> ema) {
-  const AdamHost h = check_adam(p, g, m, v, table, tens, state, stats, clock,
-                                lr_dev, ema, b1, b2, eps);
-  if (h.d.T == 0) return;
-  float* const none = nullptr;
-  if (h.e)
-    ADAM_TILES(kFused, true, none, none);
-  else
-    ADAM_TILES(kFused, false, none, none);
+  adaptive_step(nullptr, p, g, m, v, table, tens, state, stats, clock, lr_dev,
+                lr, b1, b2, eps, wd, gscale, max_norm, ema);
 }
 
 void lamb_step(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v,
@@ -339,22 +319,6 @@ void lamb_step(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v,
                c10::optional<at::Tensor> lr_dev, double lr, double b1,
                double b2, double eps, double wd, double gscale,
                double max_norm, c10::optional<at::Tensor> ema) {
-  const AdamHost h = check_adam(p, g, m, v, table, tens, state, stats, clock,
-                                lr_dev, ema, b1, b2, eps);
-  check_f32(slab, "plan slab", 2L * h.d.T);
-  if (h.d.T == 0) return;
-  float* sw = slab.data_ptr<float>();
-  float* su = sw + h.d.T;
-  float* const none = nullptr;
-  ADAM_TILES(kMoments, false, sw, su);
-  hipLaunchKernelGGL(lamb_finalise_kernel, dim3(1), dim3(kFinThreads), 0,
-                     cur_stream(), sw, su, h.d.T,
-                     reinterpret_cast<const int4v*>(tens.data_ptr<int>()),
-                     h.d.S, state.data_ptr<float>(), stats.data_ptr<float>());
-  if (h.e)
-    ADAM_TILES(kApply, true, none, none);
-  else
-    ADAM_TILES(kApply, false, none, none);
+  adaptive_step(&slab, p, g, m, v, table, tens, state, stats, clock, lr_dev,
+                lr, b1, b2, eps, wd, gscale, max_norm, ema);
 }
-
-#undef ADAM_TILES

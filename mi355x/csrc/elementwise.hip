@@ -2,6 +2,7 @@
 // All memory-bound: vectorized 16 B/lane accesses, grid-stride loops capped
 // at ~2048 workgroups (guide Guideline 11/13).
 #include "common.h"
+#include "guard.h"
 
 namespace {
 
@@ -39,18 +40,16 @@ __global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g,
       float4v vm = *reinterpret_cast<const float4v*>(m + i);
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        float gr = vg[k] * gscale + wd * vp[k];
-        vm[k] = mu * vm[k] + gr;
-        vp[k] -= lr * vm[k];
+        float a = vp[k], b = vm[k];
+        sgd_elem(a, vg[k], b, gscale, wd, mu, lr);
+        vp[k] = a;
+        vm[k] = b;
       }
       *reinterpret_cast<float4v*>(m + i) = vm;
       *reinterpret_cast<float4v*>(p + i) = vp;
     } else {
-      for (long k = i; k < n; ++k) {
-        float gr = g[k] * gscale + wd * p[k];
-        m[k] = mu * m[k] + gr;
-        p[k] -= lr * m[k];
-      }
+      for (long k = i; k < n; ++k)
+        sgd_elem(p[k], g[k], m[k], gscale, wd, mu, lr);
     }
   }
 }

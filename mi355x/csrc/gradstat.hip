@@ -57,6 +57,7 @@
 // loop, at most 2048 workgroups, scalar tail.
 #include "common.h"
 #include "guard.h"
+#include "reduce.h"
 
 #include <climits>
 #include <cmath>
@@ -87,29 +88,17 @@ __global__ __launch_bounds__(256) void grad_stats_kernel(
       }
     }
   }
-  float s = (acc[0] + acc[1]) + (acc[2] + acc[3]);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    s += __shfl_xor(s, off, kWave);
-    bad += __shfl_xor(bad, off, kWave);
-  }
-  __shared__ float ls[4];
-  __shared__ int lb[4];
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    ls[wave] = s;
-    lb[wave] = bad;
-  }
-  __syncthreads();
+  float s = sum4(acc[0], acc[1], acc[2], acc[3]);
+  block_sum256(s, bad);
   if (threadIdx.x == 0) {
-    slab_sq[blockIdx.x] = (ls[0] + ls[1]) + (ls[2] + ls[3]);
-    slab_nf[blockIdx.x] = (lb[0] + lb[1]) + (lb[2] + lb[3]);
+    slab_sq[blockIdx.x] = s;
+    slab_nf[blockIdx.x] = bad;
   }
 }
 
 // one block: slab -> out[0] = non-finite count (int32 bits), out[1] = norm.
-// Thread t adds entries t, t+256, ... in double, then a butterfly and four
-// LDS slots: one fixed order whatever the grid of pass 1 was doing.
+// Thread t adds entries t, t+256, ... in double, then the block sum
+// (reduce.h): one fixed order whatever the grid of pass 1 was doing.
 __global__ __launch_bounds__(256) void grad_stats_finalise_kernel(
     const float* __restrict__ slab_sq, const int* __restrict__ slab_nf, int nb,
     float* __restrict__ out) {
@@ -119,24 +108,10 @@ __global__ __launch_bounds__(256) void grad_stats_finalise_kernel(
     s += (double)slab_sq[j];
     c += slab_nf[j];
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    s += __shfl_xor(s, off, kWave);
-    c += __shfl_xor(c, off, kWave);
-  }
-  __shared__ double ls[4];
-  __shared__ long long lc[4];
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    ls[wave] = s;
-    lc[wave] = c;
-  }
-  __syncthreads();
+  block_sum256(s, c);
   if (threadIdx.x == 0) {
-    const double tot = (ls[0] + ls[1]) + (ls[2] + ls[3]);
-    const long long cnt = (lc[0] + lc[1]) + (lc[2] + lc[3]);
-    reinterpret_cast<int*>(out)[0] = (int)(cnt > INT_MAX ? INT_MAX : cnt);
-    out[1] = (float)sqrt(tot);
+    reinterpret_cast<int*>(out)[0] = (int)(c > INT_MAX ? INT_MAX : c);
+    out[1] = (float)sqrt(s);
   }
 }
 
@@ -169,13 +144,14 @@ __global__ void sgd_guarded_kernel(float* __restrict__ p,
       if constexpr (kEma) ve = *reinterpret_cast<const float4v*>(e + i);
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        float gr = vg[k] * gscale + wd * vp[k];
-        vm[k] = mu * vm[k] + gr;
-        vp[k] -= lr * vm[k];
+        float a = vp[k], b = vm[k];
+        sgd_elem(a, vg[k], b, gscale, wd, mu, lr);
+        vp[k] = a;
+        vm[k] = b;
         if constexpr (kEma) {
-          float a = ve[k];
-          ema_elem(a, vp[k], omd);
-          ve[k] = a;
+          float c = ve[k];
+          ema_elem(c, a, omd);
+          ve[k] = c;
         }
       }
       *reinterpret_cast<float4v*>(m + i) = vm;
@@ -183,9 +159,7 @@ __global__ void sgd_guarded_kernel(float* __restrict__ p,
       if constexpr (kEma) *reinterpret_cast<float4v*>(e + i) = ve;
     } else {
       for (long k = i; k < n; ++k) {
-        float gr = g[k] * gscale + wd * p[k];
-        m[k] = mu * m[k] + gr;
-        p[k] -= lr * m[k];
+        sgd_elem(p[k], g[k], m[k], gscale, wd, mu, lr);
         if constexpr (kEma) ema_elem(e[k], p[k], omd);
       }
     }
@@ -277,21 +251,14 @@ void sgd_step_guarded(at::Tensor p, at::Tensor g, at::Tensor m,
               "p, g and m must have the same number of elements");
   const float* lr_ptr = lr_dev.has_value() ? check_dev_scalar(*lr_dev, p)
                                            : nullptr;
-  const dim3 grid(gs_grid(n)), block(256);
-  if (ema.has_value()) {
-    const EmaArgs a = check_ema(*ema, clock, p);
-    hipLaunchKernelGGL(sgd_guarded_kernel<true>, grid, block, 0, cur_stream(),
-                       p.data_ptr<float>(), g.data_ptr<float>(),
-                       m.data_ptr<float>(), n, state.data_ptr<float>(), lr_ptr,
-                       (float)lr, (float)mu, (float)wd, (float)gscale,
-                       (float)max_norm, a.e, a.clock);
-    return;
-  }
-  hipLaunchKernelGGL(sgd_guarded_kernel<false>, grid, block, 0, cur_stream(),
-                     p.data_ptr<float>(), g.data_ptr<float>(),
-                     m.data_ptr<float>(), n, state.data_ptr<float>(), lr_ptr,
-                     (float)lr, (float)mu, (float)wd, (float)gscale,
-                     (float)max_norm, (float*)nullptr, (const float*)nullptr);
+  EmaArgs a = {nullptr, nullptr};
+  if (ema.has_value()) a = check_ema(*ema, clock, p);
+  pick<true, false>(ema.has_value(), [&](auto kEma) {
+    launch256(sgd_guarded_kernel<kEma>, dim3(gs_grid(n)), 0,
+              p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), n,
+              state.data_ptr<float>(), lr_ptr, lr, mu, wd, gscale, max_norm,
+              a.e, a.clock);
+  });
 }
 
 void clock_advance(at::Tensor clock, c10::optional<at::Tensor> state,

@@ -1,6 +1,8 @@
 // The guard state shared by the guarded optimizer steps (gradstat.hip,
-// lars.hip): its layout, the multiplier derived from it, and the non-finite
-// test. Layout and rules are documented at the top of gradstat.hip.
+// lars.hip, adam.hip): its layout, the multiplier derived from it and the
+// non-finite test; and the per-element SGD and EMA updates that more than
+// one kernel applies. Layout and rules are documented at the top of
+// gradstat.hip.
 #pragma once
 
 #include "common.h"
@@ -29,6 +31,16 @@ enum ClockField {
   kClkEmaOmd = 2,
   kClkLen = 4,
 };
+
+// SGD with momentum, for sgd_kernel and sgd_guarded_kernel alike (gs: the
+// gradient multiplier). No contraction pragma: the compiler contracts this
+// to wd * p and three fmas, and lars_elem spells out that fused form.
+DEV_INLINE void sgd_elem(float& p, float g, float& m, float gs, float wd,
+                         float mu, float lr) {
+  const float gr = g * gs + wd * p;
+  m = mu * m + gr;
+  p -= lr * m;
+}
 
 // e += omd * (w - e), w the weight just written. The roundings spelled out
 // as in lars_elem, so every update kernel averages alike.

@@ -25,6 +25,10 @@
 // 16 B/lane body and a scalar tail. The buffers themselves must be 16-byte
 // aligned.
 //
+// The plan's constants, the tile decode, the per-tensor combine and the
+// argument checks are in tile_plan.h (adam.hip walks the same plan); the
+// block sum of pass 1 is reduce.h's, as in gradstat.hip.
+//
 // As in gradstat.hip: no float atomics, no last-block ticket. A tile's
 // partial is formed by one block in one order and pass 1 only strides over
 // tiles, so every norm and trust ratio is bit-identical from run to run,
@@ -43,9 +47,7 @@ __global__ __launch_bounds__(256) void lars_partials_kernel(
     const float* __restrict__ w, const float* __restrict__ g, long n,
     const int4v* __restrict__ table, int T, int S, float* __restrict__ slab_w,
     float* __restrict__ slab_g, int* __restrict__ slab_nf) {
-  __shared__ float lw[4], lg[4];
-  __shared__ int lb[4];
-  const int tid = threadIdx.x, wave = tid >> 6;
+  const int tid = threadIdx.x;
   for (int t = blockIdx.x; t < T; t += gridDim.x) {
     const Tile q = load_tile(table, t, n, S);
     float4v aw = {0.f, 0.f, 0.f, 0.f}, ag = {0.f, 0.f, 0.f, 0.f};
@@ -83,24 +85,13 @@ __global__ __launch_bounds__(256) void lars_partials_kernel(
         bad += non_finite(b);
       }
     }
-    float sw = (aw[0] + aw[1]) + (aw[2] + aw[3]);
-    float sg = (ag[0] + ag[1]) + (ag[2] + ag[3]);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      sw += __shfl_xor(sw, off, kWave);
-      sg += __shfl_xor(sg, off, kWave);
-      bad += __shfl_xor(bad, off, kWave);
-    }
-    if ((tid & 63) == 0) {
-      lw[wave] = sw;
-      lg[wave] = sg;
-      lb[wave] = bad;
-    }
-    __syncthreads();
+    float sw = sum4(aw[0], aw[1], aw[2], aw[3]);
+    float sg = sum4(ag[0], ag[1], ag[2], ag[3]);
+    block_sum256(sw, sg, bad);
     if (tid == 0) {
-      slab_w[t] = (lw[0] + lw[1]) + (lw[2] + lw[3]);
-      slab_g[t] = (lg[0] + lg[1]) + (lg[2] + lg[3]);
-      slab_nf[t] = (lb[0] + lb[1]) + (lb[2] + lb[3]);
+      slab_w[t] = sw;
+      slab_g[t] = sg;
+      slab_nf[t] = bad;
     }
     __syncthreads();  // the LDS slots are reused by the next tile
   }
@@ -119,9 +110,9 @@ DEV_INLINE float trust_ratio(float wn, float gn_raw, float eff, float wd,
   return num / den;
 }
 
-// One block. Wave v owns tensors v, v+16, ...: lane l adds the tensor's
-// tiles l, l+64, ... in double, then a butterfly. Wave 0 then adds the
-// per-tensor g sums the same way. One fixed order whatever pass 1's grid.
+// One block. combine_tiles (tile_plan.h) adds each tensor's tiles, then wave
+// 0 adds the per-tensor g sums the same way: lane l takes tensors l, l+64,
+// ... in double, then a butterfly. One fixed order whatever pass 1's grid.
 __global__ __launch_bounds__(kFinThreads) void lars_finalise_kernel(
     const float* __restrict__ slab_w, const float* __restrict__ slab_g,
     const int* __restrict__ slab_nf, int T, const int4v* __restrict__ tens,
@@ -134,25 +125,14 @@ __global__ __launch_bounds__(kFinThreads) void lars_finalise_kernel(
   double* sum_w = lsum;
   double* sum_g = lsum + S;
 
-  for (int s = wave; s < S; s += kFinWaves) {
-    const int4v e = tens[s];
-    const int t0 = max(e[0], 0), t1 = min(e[1], T);
-    double a = 0.0, b = 0.0;
-    for (int t = t0 + lane; t < t1; t += kWave) {
-      a += (double)slab_w[t];
-      b += (double)slab_g[t];
-    }
-    a = wave_sum(a);
-    b = wave_sum(b);
-    if (lane == 0) {
-      sum_w[s] = a;
-      sum_g[s] = b;
-    }
-  }
+  combine_tiles(slab_w, slab_g, T, tens, S,
+                [&](int s, const int4v&, double a, double b) {
+                  sum_w[s] = a;
+                  sum_g[s] = b;
+                });
   long long c = 0;
   for (int t = tid; t < T; t += kFinThreads) c += slab_nf[t];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off, kWave);
+  c = wave_sum(c);
   if (lane == 0) lc[wave] = c;
   __syncthreads();
 
@@ -276,24 +256,19 @@ void lars_stats(at::Tensor p, at::Tensor g, at::Tensor table, at::Tensor tens,
                 at::Tensor slab, at::Tensor state, at::Tensor stats,
                 double gscale, double max_norm, double wd, double eta,
                 double eps) {
-  const long n = p.numel();
-  check_flat(p, "p", n);
-  check_flat(g, "g", n);
-  check_f32(state, "state", kStateLen);
-  const PlanDims d = check_plan(table, tens, stats, n);
+  const PlanDims d = check_plan(p, g, state, table, tens, stats);
   check_f32(slab, "plan slab", 3L * d.T);
   float* sw = slab.data_ptr<float>();
   float* sg = sw + d.T;
   int* nf = reinterpret_cast<int*>(sg + d.T);
-  const int4v* tb = reinterpret_cast<const int4v*>(table.data_ptr<int>());
-  const int4v* tn = reinterpret_cast<const int4v*>(tens.data_ptr<int>());
   if (d.T > 0)
-    hipLaunchKernelGGL(lars_partials_kernel, dim3(d.grid), dim3(256), 0,
-                       cur_stream(), p.data_ptr<float>(), g.data_ptr<float>(),
-                       n, tb, d.T, d.S, sw, sg, nf);
+    launch256(lars_partials_kernel, dim3(d.grid), 0, p.data_ptr<float>(),
+              g.data_ptr<float>(), p.numel(), int4_rows(table), d.T, d.S, sw,
+              sg, nf);
   hipLaunchKernelGGL(lars_finalise_kernel, dim3(1), dim3(kFinThreads),
                      2 * d.S * sizeof(double), cur_stream(), sw, sg, nf, d.T,
-                     tn, d.S, state.data_ptr<float>(), stats.data_ptr<float>(),
+                     int4_rows(tens), d.S, state.data_ptr<float>(),
+                     stats.data_ptr<float>(),
                      (float)gscale, (float)max_norm, (float)wd, (float)eta,
                      (float)eps);
 }
@@ -304,28 +279,18 @@ void lars_step(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor table,
                double wd, double gscale, double max_norm,
                c10::optional<at::Tensor> ema,
                c10::optional<at::Tensor> clock) {
-  const long n = p.numel();
-  check_flat(p, "p", n);
-  check_flat(g, "g", n);
-  check_flat(m, "m", n);
-  check_f32(state, "state", kStateLen);
-  const PlanDims d = check_plan(table, tens, stats, n);
+  const PlanDims d = check_plan(p, g, state, table, tens, stats);
+  check_flat(m, "m", p.numel());
   const float* lr_ptr = lr_dev.has_value() ? check_dev_scalar(*lr_dev, p)
                                            : nullptr;
   EmaArgs a = {nullptr, nullptr};
   if (ema.has_value()) a = check_ema(*ema, clock, p);
   if (d.T == 0) return;
-#define LARS_UPDATE(EMA)                                                     \
-  hipLaunchKernelGGL(                                                        \
-      lars_update_kernel<EMA>, dim3(d.grid), dim3(256), 0, cur_stream(),     \
-      p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), n,      \
-      reinterpret_cast<const int4v*>(table.data_ptr<int>()), d.T,            \
-      reinterpret_cast<const int4v*>(tens.data_ptr<int>()), d.S,             \
-      state.data_ptr<float>(), stats.data_ptr<float>(), lr_ptr, (float)lr,   \
-      (float)mu, (float)wd, (float)gscale, (float)max_norm, a.e, a.clock)
-  if (ema.has_value())
-    LARS_UPDATE(true);
-  else
-    LARS_UPDATE(false);
-#undef LARS_UPDATE
+  pick<true, false>(ema.has_value(), [&](auto kEma) {
+    launch256(lars_update_kernel<kEma>, dim3(d.grid), 0, p.data_ptr<float>(),
+              g.data_ptr<float>(), m.data_ptr<float>(), p.numel(),
+              int4_rows(table), d.T, int4_rows(tens), d.S,
+              state.data_ptr<float>(), stats.data_ptr<float>(), lr_ptr, lr, mu,
+              wd, gscale, max_norm, a.e, a.clock);
+  });
 }

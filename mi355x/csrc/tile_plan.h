@@ -1,10 +1,12 @@
 // The tile plan over the flat fp32 buffers that lars.hip and adam.hip walk:
-// its constants, the per-tile decode and the host-side checks. The plan's
-// layout is documented at the top of lars.hip.
+// its constants, the per-tile decode, the per-tensor combine of the per-tile
+// sums and the host-side checks. The plan's layout is documented at the top
+// of lars.hip.
 #pragma once
 
 #include "common.h"
 #include "guard.h"
+#include "reduce.h"
 
 #include <climits>
 #include <cstdint>
@@ -37,10 +39,28 @@ DEV_INLINE Tile load_tile(const int4v* __restrict__ table, int t, long n,
   return {ok, (long)e[0], head, nvec, e[1] - head - 4 * nvec, e[2]};
 }
 
-DEV_INLINE double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
-  return v;
+// The per-tensor combine of two per-tile slabs, by one block of kFinThreads:
+// wave v owns tensors v, v+16, ...; lane l adds the tensor's tiles l, l+64,
+// ... in double, then a butterfly. Lane 0 hands the sums to done(s, tens[s],
+// sum_a, sum_b). One fixed order whatever the grid that filled the slabs.
+template <typename F>
+DEV_INLINE void combine_tiles(const float* __restrict__ slab_a,
+                              const float* __restrict__ slab_b, int T,
+                              const int4v* __restrict__ tens, int S,
+                              F&& done) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  for (int s = wave; s < S; s += kFinWaves) {
+    const int4v e = tens[s];
+    const int t0 = max(e[0], 0), t1 = min(e[1], T);
+    double a = 0.0, b = 0.0;
+    for (int t = t0 + lane; t < t1; t += kWave) {
+      a += (double)slab_a[t];
+      b += (double)slab_b[t];
+    }
+    a = wave_sum(a);
+    b = wave_sum(b);
+    if (lane == 0) done(s, e, a, b);
+  }
 }
 
 inline void check_i32x4(const at::Tensor& t, const char* name) {
@@ -48,6 +68,11 @@ inline void check_i32x4(const at::Tensor& t, const char* name) {
   TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
   TORCH_CHECK(t.scalar_type() == at::kInt, name, " must be int32");
   TORCH_CHECK(t.dim() == 2 && t.size(1) == 4, name, " must be [rows, 4]");
+}
+
+// the rows of a checked plan table as the kernels read them
+inline const int4v* int4_rows(const at::Tensor& t) {
+  return reinterpret_cast<const int4v*>(t.data_ptr<int>());
 }
 
 inline void check_flat(const at::Tensor& t, const char* name, long n) {
@@ -62,8 +87,14 @@ struct PlanDims {
   int T, S, grid;
 };
 
-inline PlanDims check_plan(const at::Tensor& table, const at::Tensor& tens,
-                           const at::Tensor& stats, long n) {
+// what every plan entry point takes: p and g, the guard state and the plan
+inline PlanDims check_plan(const at::Tensor& p, const at::Tensor& g,
+                           const at::Tensor& state, const at::Tensor& table,
+                           const at::Tensor& tens, const at::Tensor& stats) {
+  const long n = p.numel();
+  check_flat(p, "p", n);
+  check_flat(g, "g", n);
+  check_f32(state, "state", kStateLen);
   check_i32x4(table, "plan table");
   check_i32x4(tens, "plan tensor table");
   const long T = table.size(0), S = tens.size(0);

@@ -1389,31 +1389,42 @@ def _guard_coef(state, grad_scale, max_norm):
     return norm, coef, k * coef
 
 
-def _lr_tensor(lr, flat_param, who):
-    """lr as the update kernels take it: None for a float, else the checked
-    one-element float32 tensor on the buffers' device."""
+def _split_lr(lr, flat_param, who):
+    """lr as the update kernels take it, (tensor, float): (None, lr) for a
+    float, else (the checked one-element float32 tensor on the buffers'
+    device, 0.0)."""
     if not isinstance(lr, torch.Tensor):
-        return None
+        return None, lr
     if (lr.numel() != 1 or lr.dtype != torch.float32
             or lr.device != flat_param.device):
         raise ValueError(f"{who}: a tensor lr must be one float32 element "
                          "on the buffers' device")
-    return lr
+    return lr, 0.0
+
+
+def _check_clock(clock, flat_param, who, user):
+    if (clock is None or clock.numel() < CK_LEN
+            or clock.dtype != torch.float32
+            or clock.device != flat_param.device):
+        raise ValueError(f"{who}: {user} needs the step clock, "
+                         f"float32[{CK_LEN}] on the buffers' device")
 
 
 def _check_ema(ema, clock, flat_param, who):
     if ema is None:
         return
-    if clock is None:
-        raise ValueError(f"{who}: an EMA update needs the step clock")
+    _check_clock(clock, flat_param, who, "an EMA update")
     if (ema.shape != flat_param.shape or ema.dtype != torch.float32
             or ema.device != flat_param.device):
         raise ValueError(f"{who}: ema must be float32 with the parameters' "
                          "shape and device")
-    if (clock.numel() < CK_LEN or clock.dtype != torch.float32
-            or clock.device != flat_param.device):
-        raise ValueError(f"{who}: the clock must be float32[{CK_LEN}] on the "
-                         "buffers' device")
+
+
+def _tensor_sumsq(plan, x):
+    """Per tensor of the plan, the sum of squares of its slice of the flat
+    ``x``, in float64: [S]."""
+    return torch.stack([x[a:b].double().square().sum()
+                        for a, b in zip(plan.offsets, plan.offsets[1:])])
 
 
 def _ema_update_cpu(ema, flat_param, clock):
@@ -1441,13 +1452,13 @@ def sgd_step_guarded(flat_param, flat_grad, flat_momentum, state, lr,
     parameters' layout) the same pass also does ``e += omd * (w_new - e)``,
     omd = ``clock[CK_EMA_OMD]``; a skipped step leaves ``ema`` alone too."""
     max_norm = float(max_norm)
-    lr_t = _lr_tensor(lr, flat_param, "sgd_step_guarded")
+    lr_t, lr_f = _split_lr(lr, flat_param, "sgd_step_guarded")
     _check_ema(ema, clock, flat_param, "sgd_step_guarded")
     if flat_param.is_cuda:
         ext().sgd_step_guarded(flat_param, flat_grad, flat_momentum, state,
-                               lr_t, 0.0 if lr_t is not None else lr,
-                               momentum, weight_decay, grad_scale, max_norm,
-                               ema, clock if ema is not None else None)
+                               lr_t, lr_f, momentum, weight_decay, grad_scale,
+                               max_norm, ema,
+                               clock if ema is not None else None)
         return
     if int(state.view(torch.int32)[GS_NONFINITE]) != 0:
         return
@@ -1657,18 +1668,15 @@ def lars_stats(flat_param, flat_grad, plan, state, grad_scale=1.0,
                          weight_decay, eta, eps)
         return plan.stats
     f32 = lambda v: torch.tensor(v, dtype=torch.float32)  # noqa: E731
-    S = len(plan.exclude)
-    sums = torch.zeros(S, 2, dtype=torch.float64)
-    for s, (a, b) in enumerate(zip(plan.offsets, plan.offsets[1:])):
-        sums[s, 0] = flat_param[a:b].double().square().sum()
-        sums[s, 1] = flat_grad[a:b].double().square().sum()
+    sum_w = _tensor_sumsq(plan, flat_param)
+    sum_g = _tensor_sumsq(plan, flat_grad)
     state.view(torch.int32)[GS_NONFINITE] = (
         ~torch.isfinite(flat_grad)).sum().clamp(max=2**31 - 1)
-    state[GS_RAW_NORM] = sums[:, 1].sum().sqrt()
+    state[GS_RAW_NORM] = sum_g.sum().sqrt()
     _, _, eff = _guard_coef(state, grad_scale, max_norm)
     # float32, one rounding per op, in lars.hip's trust_ratio order
-    wn = sums[:, 0].sqrt().float()
-    gn_raw = sums[:, 1].sqrt().float()
+    wn = sum_w.sqrt().float()
+    gn_raw = sum_g.sqrt().float()
     gn = gn_raw * eff
     den = (gn + f32(weight_decay) * wn) + f32(eps)
     trust = (f32(eta) * wn) / den
@@ -1696,12 +1704,11 @@ def lars_step(flat_param, flat_grad, flat_momentum, plan, state, lr,
     ``clock[CK_EMA_OMD]``; a skipped step leaves ``ema`` alone too."""
     max_norm = float(max_norm)
     plan.check(flat_param, flat_grad, flat_momentum)
-    lr_t = _lr_tensor(lr, flat_param, "lars_step")
+    lr_t, lr_f = _split_lr(lr, flat_param, "lars_step")
     _check_ema(ema, clock, flat_param, "lars_step")
     if flat_param.is_cuda:
         ext().lars_step(flat_param, flat_grad, flat_momentum, plan.table,
-                        plan.tens, state, plan.stats, lr_t,
-                        0.0 if lr_t is not None else lr, momentum,
+                        plan.tens, state, plan.stats, lr_t, lr_f, momentum,
                         weight_decay, grad_scale, max_norm, ema,
                         clock if ema is not None else None)
         return
@@ -1752,17 +1759,12 @@ def _adaptive_step(who, flat_param, flat_grad, exp_avg, exp_avg_sq, plan,
         raise ValueError(f"{who}: weight_decay must be >= 0, got "
                          f"{weight_decay}")
     plan.check(flat_param, flat_grad, exp_avg, exp_avg_sq)
-    lr_t = _lr_tensor(lr, flat_param, who)
-    if (clock is None or clock.numel() < CK_LEN
-            or clock.dtype != torch.float32
-            or clock.device != flat_param.device):
-        raise ValueError(f"{who}: needs the step clock, float32[{CK_LEN}] on "
-                         "the buffers' device (bias correction reads it)")
+    lr_t, lr_f = _split_lr(lr, flat_param, who)
+    _check_clock(clock, flat_param, who, "the bias correction")
     _check_ema(ema, clock, flat_param, who)
     if flat_param.is_cuda:
-        args = (state, plan.stats, clock, lr_t,
-                0.0 if lr_t is not None else lr, b1, b2, eps, weight_decay,
-                grad_scale, max_norm, ema)
+        args = (state, plan.stats, clock, lr_t, lr_f, b1, b2, eps,
+                weight_decay, grad_scale, max_norm, ema)
         if lamb:
             ext().lamb_step(flat_param, flat_grad, exp_avg, exp_avg_sq,
                             plan.table, plan.tens, plan.slab, *args)
@@ -1785,12 +1787,8 @@ def _adaptive_step(who, flat_param, flat_grad, exp_avg, exp_avg_sq, plan,
     u = (exp_avg * rbc1).div_(den).add_(plan.per_element(wd) * flat_param)
     step = lr_t.reshape(()) if lr_t is not None else lr
     if lamb:
-        S = len(plan.exclude)
-        sums = torch.zeros(S, 2, dtype=torch.float64)
-        for s, (a, b) in enumerate(zip(plan.offsets, plan.offsets[1:])):
-            sums[s, 0] = flat_param[a:b].double().square().sum()
-            sums[s, 1] = u[a:b].double().square().sum()
-        wn, un = sums[:, 0].sqrt().float(), sums[:, 1].sqrt().float()
+        wn = _tensor_sumsq(plan, flat_param).sqrt().float()
+        un = _tensor_sumsq(plan, u).sqrt().float()
         keep = (wn > 0) & (un > 0) & ~plan._excluded
         plan.stats[:, LAMB_WNORM] = wn
         plan.stats[:, LAMB_UNORM] = un

@@ -176,8 +176,77 @@ class EMA:
 
 
 class _Clocked:
-    """What optim.SGD and optim.LARS share: the step clock behind an
-    LRSchedule and an EMA, and its part of the checkpoint."""
+    """What the optimizers share: the step clock behind an LRSchedule and an
+    EMA with its part of the checkpoint, the guarded-step protocol around
+    the update kernels, and the tile plan of the flat layout."""
+
+    def _init_guard(self, grad_scale, max_grad_norm):
+        self.grad_scale = grad_scale
+        self.max_grad_norm = max_grad_norm
+        # made on first use: the clip-only guard state (a DeviceGradScaler
+        # brings its own) and grad_stats' slab
+        self._own_state = None
+        self._slab = None
+        self._guard_state = None  # the state the last guarded step used
+
+    def _init_plan(self, exclude):
+        """``exclude``: a predicate on the parameter (default: ndim <= 1)."""
+        if exclude is None:
+            exclude = lambda p: p.ndim <= 1  # noqa: E731
+        flat = self.flat
+        spans = [flat.offsets[id(p)] for p in flat.params]
+        self.plan = ops.lars_plan(
+            [0] + [e for _, e in spans], [bool(exclude(p)) for p in flat.params],
+            flat.flat_param.device)
+
+    def _begin_guarded(self, scaler):
+        """-> (guard state, the scaler's (growth, backoff, interval), max_norm
+        as a float) for one guarded step."""
+        if scaler is not None:
+            state = scaler.state
+            dyn = (scaler.growth_factor, scaler.backoff_factor,
+                   scaler.growth_interval)
+        else:
+            if self._own_state is None:
+                self._own_state = _fn.new_guard_state(
+                    self.flat.flat_grad.device)
+            state = self._own_state
+            dyn = (1.0, 1.0, 0)  # no loss scale to move
+        self._guard_state = state
+        max_norm = (float("inf") if self.max_grad_norm is None
+                    else float(self.max_grad_norm))
+        return state, dyn, max_norm
+
+    def _grad_stats(self, state):
+        g = self.flat.flat_grad
+        if g.is_cuda and self._slab is None:
+            self._slab = torch.empty(_fn.GRAD_STATS_SLAB, dtype=torch.float32,
+                                     device=g.device)
+        ops.grad_stats(g, slab=self._slab,
+                       out=state[_fn.GS_NONFINITE:_fn.GS_RAW_NORM + 1])
+
+    def _end_guarded(self, state, dyn, max_norm):
+        ops.scaler_update(state, self.grad_scale, max_norm, *dyn)
+        self._advance_clock(state)
+        _fn.bump_cache_epoch()  # invalidate cached 16-bit weight copies
+
+    @property
+    def last_grad_norm(self):
+        """Norm of the true gradient (unscaled, world-averaged) at the last
+        guarded step, before clipping: a 0-d device tensor, no sync."""
+        if self._guard_state is None:
+            raise RuntimeError("last_grad_norm: no guarded step taken yet")
+        return self._guard_state[_fn.GS_LAST_NORM]
+
+    @property
+    def skipped_steps(self) -> int:
+        """Steps skipped for an inf/nan gradient so far (syncs; for logs)."""
+        if self._guard_state is None:
+            return 0
+        return int(self._guard_state.view(torch.int32)[_fn.GS_SKIPPED].item())
+
+    def zero_grad(self, set_to_none: bool = False):
+        self.flat.zero_grad()
 
     def _init_clock(self, lr, ema, force=False):
         """``force``: keep a clock even with no schedule and no EMA (AdamW
@@ -266,69 +335,24 @@ class SGD(_Clocked):
                  max_grad_norm: float | None = None, ema: EMA | None = None):
         self.flat = flat
         self._init_clock(lr, ema)
+        self._init_guard(grad_scale, max_grad_norm)
         self.momentum = momentum
         self.weight_decay = weight_decay
-        self.grad_scale = grad_scale
-        self.max_grad_norm = max_grad_norm
-        # guarded path only, made on first use: the clip-only guard state
-        # (a DeviceGradScaler brings its own) and the reduction's slab
-        self._own_state = None
-        self._slab = None
-        self._guard_state = None  # the state the last guarded step used
 
     def step(self, scaler=None):
+        f = self.flat
         if (scaler is None and self.max_grad_norm is None
                 and self.clock is None):
-            ops.sgd_step(self.flat.flat_param, self.flat.flat_grad,
-                         self.flat.flat_momentum, self.lr, self.momentum,
-                         self.weight_decay, self.grad_scale)
-        else:
-            self._guarded_step(scaler)
-        _fn.bump_cache_epoch()  # invalidate cached 16-bit weight copies
-
-    def _guarded_step(self, scaler):
-        g = self.flat.flat_grad
-        if scaler is not None:
-            state = scaler.state
-            dyn = (scaler.growth_factor, scaler.backoff_factor,
-                   scaler.growth_interval)
-        else:
-            if self._own_state is None:
-                self._own_state = _fn.new_guard_state(g.device)
-            state = self._own_state
-            dyn = (1.0, 1.0, 0)  # no loss scale to move
-        if g.is_cuda and self._slab is None:
-            self._slab = torch.empty(_fn.GRAD_STATS_SLAB, dtype=torch.float32,
-                                     device=g.device)
-        self._guard_state = state
-        max_norm = (float("inf") if self.max_grad_norm is None
-                    else float(self.max_grad_norm))
-        ops.grad_stats(g, slab=self._slab,
-                       out=state[_fn.GS_NONFINITE:_fn.GS_RAW_NORM + 1])
-        ops.sgd_step_guarded(self.flat.flat_param, g, self.flat.flat_momentum,
+            ops.sgd_step(f.flat_param, f.flat_grad, f.flat_momentum, self.lr,
+                         self.momentum, self.weight_decay, self.grad_scale)
+            _fn.bump_cache_epoch()  # invalidate cached 16-bit weight copies
+            return
+        state, dyn, max_norm = self._begin_guarded(scaler)
+        self._grad_stats(state)
+        ops.sgd_step_guarded(f.flat_param, f.flat_grad, f.flat_momentum,
                              state, self.lr, self.momentum, self.weight_decay,
                              self.grad_scale, max_norm, **self._ema_kw())
-        ops.scaler_update(state, self.grad_scale, max_norm, *dyn)
-        self._advance_clock(state)
-
-    @property
-    def last_grad_norm(self):
-        """Norm of the true gradient (unscaled, world-averaged) at the last
-        guarded step, before clipping: a 0-d device tensor, no sync."""
-        if self._guard_state is None:
-            raise RuntimeError("last_grad_norm: no guarded step taken yet "
-                               "(set max_grad_norm or pass a scaler)")
-        return self._guard_state[_fn.GS_LAST_NORM]
-
-    @property
-    def skipped_steps(self) -> int:
-        """Steps skipped for an inf/nan gradient so far (syncs; for logs)."""
-        if self._guard_state is None:
-            return 0
-        return int(self._guard_state.view(torch.int32)[_fn.GS_SKIPPED].item())
-
-    def zero_grad(self, set_to_none: bool = False):
-        self.flat.zero_grad()
+        self._end_guarded(state, dyn, max_norm)
 
     def state_dict(self):
         lr = float(self.lr) if self.schedule is not None else self.lr
@@ -379,68 +403,29 @@ class LARS(_Clocked):
                  max_grad_norm: float | None = None, ema: EMA | None = None):
         self.flat = flat
         self._init_clock(lr, ema)
+        self._init_guard(grad_scale, max_grad_norm)
+        self._init_plan(exclude)
         self.momentum = momentum
         self.weight_decay = weight_decay
         self.trust_coefficient = trust_coefficient
         self.eps = eps
-        self.grad_scale = grad_scale
-        self.max_grad_norm = max_grad_norm
-        if exclude is None:
-            exclude = lambda p: p.ndim <= 1  # noqa: E731
-        spans = [flat.offsets[id(p)] for p in flat.params]
-        self.plan = ops.lars_plan(
-            [0] + [e for _, e in spans], [bool(exclude(p)) for p in flat.params],
-            flat.flat_param.device)
-        self._own_state = None    # made on first use without a scaler
-        self._guard_state = None  # the state the last step used
 
     def step(self, scaler=None):
         f = self.flat
-        if scaler is not None:
-            state = scaler.state
-            dyn = (scaler.growth_factor, scaler.backoff_factor,
-                   scaler.growth_interval)
-        else:
-            if self._own_state is None:
-                self._own_state = _fn.new_guard_state(f.flat_grad.device)
-            state = self._own_state
-            dyn = (1.0, 1.0, 0)  # no loss scale to move
-        self._guard_state = state
-        max_norm = (float("inf") if self.max_grad_norm is None
-                    else float(self.max_grad_norm))
+        state, dyn, max_norm = self._begin_guarded(scaler)
         ops.lars_stats(f.flat_param, f.flat_grad, self.plan, state,
                        self.grad_scale, max_norm, self.weight_decay,
                        self.trust_coefficient, self.eps)
         ops.lars_step(f.flat_param, f.flat_grad, f.flat_momentum, self.plan,
                       state, self.lr, self.momentum, self.weight_decay,
                       self.grad_scale, max_norm, **self._ema_kw())
-        ops.scaler_update(state, self.grad_scale, max_norm, *dyn)
-        self._advance_clock(state)
-        _fn.bump_cache_epoch()  # invalidate cached 16-bit weight copies
+        self._end_guarded(state, dyn, max_norm)
 
     @property
     def last_trust_ratios(self):
         """trust_s of the last step, one per tensor in flat.params order: a
         device tensor, no sync. All 1 before the first step."""
         return self.plan.stats[:, _fn.LARS_TRUST]
-
-    @property
-    def last_grad_norm(self):
-        """Norm of the true gradient (unscaled, world-averaged) at the last
-        step, before clipping: a 0-d device tensor, no sync."""
-        if self._guard_state is None:
-            raise RuntimeError("last_grad_norm: no step taken yet")
-        return self._guard_state[_fn.GS_LAST_NORM]
-
-    @property
-    def skipped_steps(self) -> int:
-        """Steps skipped for an inf/nan gradient so far (syncs; for logs)."""
-        if self._guard_state is None:
-            return 0
-        return int(self._guard_state.view(torch.int32)[_fn.GS_SKIPPED].item())
-
-    def zero_grad(self, set_to_none: bool = False):
-        self.flat.zero_grad()
 
     def state_dict(self):
         return {"momentum_buffer": self.flat.flat_momentum,
@@ -491,55 +476,23 @@ class AdamW(_Clocked):
                  ema: EMA | None = None):
         self.flat = flat
         self._init_clock(lr, ema, force=True)
+        self._init_guard(grad_scale, max_grad_norm)
+        self._init_plan(exclude)
         self.betas = (float(betas[0]), float(betas[1]))
         self.eps = eps
         self.weight_decay = weight_decay
-        self.grad_scale = grad_scale
-        self.max_grad_norm = max_grad_norm
-        if exclude is None:
-            exclude = lambda p: p.ndim <= 1  # noqa: E731
-        spans = [flat.offsets[id(p)] for p in flat.params]
-        self.plan = ops.lars_plan(
-            [0] + [e for _, e in spans], [bool(exclude(p)) for p in flat.params],
-            flat.flat_param.device)
         self.exp_avg_sq = torch.zeros_like(flat.flat_param)
-        self._own_state = None    # made on first use without a scaler
-        self._slab = None         # grad_stats' partials, GPU only
-        self._guard_state = None  # the state the last step used
 
     def step(self, scaler=None):
         f = self.flat
-        g = f.flat_grad
-        if scaler is not None:
-            state = scaler.state
-            dyn = (scaler.growth_factor, scaler.backoff_factor,
-                   scaler.growth_interval)
-        else:
-            if self._own_state is None:
-                self._own_state = _fn.new_guard_state(g.device)
-            state = self._own_state
-            dyn = (1.0, 1.0, 0)  # no loss scale to move
-        if g.is_cuda and self._slab is None:
-            self._slab = torch.empty(_fn.GRAD_STATS_SLAB, dtype=torch.float32,
-                                     device=g.device)
-        self._guard_state = state
-        max_norm = (float("inf") if self.max_grad_norm is None
-                    else float(self.max_grad_norm))
-        ops.grad_stats(g, slab=self._slab,
-                       out=state[_fn.GS_NONFINITE:_fn.GS_RAW_NORM + 1])
-        self._update(f.flat_param, g, f.flat_momentum, self.exp_avg_sq,
-                     self.plan, state, self.clock, self.lr, self.betas,
-                     self.eps, self.weight_decay, self.grad_scale, max_norm,
+        state, dyn, max_norm = self._begin_guarded(scaler)
+        self._grad_stats(state)
+        self._update(f.flat_param, f.flat_grad, f.flat_momentum,
+                     self.exp_avg_sq, self.plan, state, self.clock, self.lr,
+                     self.betas, self.eps, self.weight_decay, self.grad_scale,
+                     max_norm,
                      ema=None if self.ema is None else self.ema.flat_ema)
-        ops.scaler_update(state, self.grad_scale, max_norm, *dyn)
-        self._advance_clock(state)
-        _fn.bump_cache_epoch()  # invalidate cached 16-bit weight copies
-
-    last_grad_norm = LARS.last_grad_norm
-    skipped_steps = LARS.skipped_steps
-
-    def zero_grad(self, set_to_none: bool = False):
-        self.flat.zero_grad()
+        self._end_guarded(state, dyn, max_norm)
 
     def state_dict(self):
         return {"exp_avg": self.flat.flat_momentum,

@@ -1,7 +1,8 @@
 """The adam.hip kernels on hardware through optim.AdamW / optim.LAMB, on the
 tensor table of _lars_common (every head/body/tail split, excluded tensors,
 zero weights, zero gradient): three steps against float64, a non-finite
-gradient in a scalar tail, and a captured step against the eager one.
+gradient in a scalar tail, untouched neighbours of padded buffers, and a
+captured step against the eager one.
 
 Observed on an MI355X (per case in profiles/r16_adam.md): w, m and v at
 most 0.041 of their line (rtol 4e-6, atol 4e-7), trust ratios at most
@@ -11,10 +12,10 @@ most 0.041 of their line (rtol 4e-6, atol 4e-7), trust ratios at most
 import pytest
 import torch
 
-from _adam_common import (CASES, OFF, compare, make, reference, run, snapshot,
-                          start)
-from _lars_common import EXCLUDE, ZERO_G, ZERO_W
-from mi355x import optim
+from _adam_common import (CASES, HP, OFF, compare, make, reference, run,
+                          snapshot, start)
+from _lars_common import EXCLUDE, ZERO_G, ZERO_W, synthetic
+from mi355x import ops, optim
 from mi355x.ops import functional as fn
 
 pytestmark = pytest.mark.gpu
@@ -59,6 +60,36 @@ def test_non_finite_gradient_writes_nothing_and_stops_the_clock(kind, bad):
     assert opt.skipped_steps == 1 and opt.clock_step == 3
     compare(end, reference(kind, w0, good, 1.0, 1e-2, EXCLUDE)[-1],
             f"{kind} around a skipped step")
+
+
+@pytest.mark.parametrize("kind", ["adamw", "lamb"])
+def test_neighbours_stay_intact(kind):
+    """test_gpu_lars' check for the passes LARS does not have: w, g, m, v
+    and the EMA buffer between 16 floats of sentinel each; one step changes
+    all but g and no sentinel."""
+    w, m, (g,) = synthetic(steps=1)
+    n, pad = OFF[-1], 16
+    src = {"w": w, "g": g, "m": m, "v": m.square(), "e": w + 1.0}
+    bufs = {}
+    for name, t in src.items():
+        b = torch.full((n + 2 * pad,), 12345.0, device="cuda")
+        b[pad:pad + n] = t.cuda()
+        bufs[name] = b
+    view = {name: b[pad:pad + n] for name, b in bufs.items()}
+    plan = ops.lars_plan(OFF, EXCLUDE, "cuda")
+    st = fn.new_guard_state("cuda")
+    clock = fn.new_clock("cuda", torch.zeros(1, device="cuda"), 0.9)
+    ops.grad_stats(view["g"], out=st[fn.GS_NONFINITE:fn.GS_RAW_NORM + 1])
+    step = ops.adam_step if kind == "adamw" else ops.lamb_step
+    step(view["w"], view["g"], view["m"], view["v"], plan, st, clock,
+         HP["lr"], HP["betas"], HP["eps"], 1e-2, HP["grad_scale"],
+         ema=view["e"])
+    assert int(st.view(torch.int32)[fn.GS_NONFINITE]) == 0
+    guard = torch.full((pad,), 12345.0)
+    for name, b in bufs.items():
+        assert torch.equal(b[:pad].cpu(), guard), name
+        assert torch.equal(b[pad + n:].cpu(), guard), name
+        assert torch.equal(view[name].cpu(), src[name]) == (name == "g"), name
 
 
 def _scheduled(kind, w0):
