@@ -1,12 +1,19 @@
-"""Device time of ops.attention (csrc/attn.hip) against two torch
+"""Device time of ops.attention (csrc/attn.hip, S <= 256) and of
+ops.flash_attention (csrc/attn_flash.hip, S <= 4096) against two torch
 comparators on the same values, from and to the packed qkv layout:
 
+  fused     ops.attention up to 256 tokens, ops.flash_attention above: what
+            layers.MultiHeadAttention calls
+  flash     ops.flash_attention where fused is the resident op (197x8x64 and
+            256x4x32 only): the measurement behind the layer's crossover
   sdpa      F.scaled_dot_product_attention, with the permute copies it needs
             from [B,S,3,H,dh] and back to [B,S,D]
   composed  torch.matmul, softmax, torch.matmul, the same copies
 
-Shapes (S, H, dh) at batch --batch, bf16: 64x4x64 (vit_cifar), 197x8x64,
-256x4x32.
+Shapes (S, H, dh), bf16: 64x4x64 (vit_cifar), 197x8x64, 256x4x32 at batch
+--batch; 577x6x64 at --batch / 8, 784x6x64 (vit_s8) and 1024x4x32 at
+--batch / 16, 4096x4x64 at --batch / 128, so that the composed arm's S^2
+scores fit.
 
   fwd_*  forward only, under no_grad
   fb_*   forward + backward into qkv.grad
@@ -22,7 +29,8 @@ forms S and dP twice, which is not counted).
     python benchmarks/attn_bench.py [--batch 1024] [--rounds 7] [--iters 10]
                                     [--out results.json]
 
-Needs a GPU: there is no CPU mode. Results: profiles/r17_attention.md.
+Needs a GPU: there is no CPU mode. Results: profiles/r17_attention.md and
+profiles/r21_flash_attention.md.
 """
 
 from __future__ import annotations
@@ -40,7 +48,10 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import mi355x.ops as ops  # noqa: E402
 
-SHAPES = [(64, 4, 64), (197, 8, 64), (256, 4, 32)]
+# (S, H, dh, batch divisor, also time ops.flash_attention)
+SHAPES = [(64, 4, 64, 1, False), (197, 8, 64, 1, True), (256, 4, 32, 1, True),
+          (577, 6, 64, 8, False), (784, 6, 64, 16, False),
+          (1024, 4, 32, 16, False), (4096, 4, 64, 128, False)]
 
 
 def _window(f, iters):
@@ -81,15 +92,18 @@ def main():
     args = ap.parse_args()
     assert torch.cuda.is_available(), "attn_bench needs a GPU"
     results = []
-    for S, H, dh in SHAPES:
-        B = args.batch
+    for S, H, dh, div, both in SHAPES:
+        B = max(1, args.batch // div)
         g = torch.Generator().manual_seed(S)
         qkv = torch.randn(B, S, 3, H, dh, generator=g).bfloat16().cuda()
         dy = torch.randn(B, S, H * dh, generator=g).bfloat16().cuda()
         leaf = qkv.clone().requires_grad_()
-        impls = {"fused": lambda t: ops.attention(t, H),
+        op = ops.attention if S <= 256 else ops.flash_attention
+        impls = {"fused": lambda t: op(t, H),
                  "sdpa": lambda t: _sdpa(t, H),
                  "composed": lambda t: _composed(t, H)}
+        if both:
+            impls["flash"] = lambda t: ops.flash_attention(t, H)
         arms = {}
         for name, f in impls.items():
             def fwd(f=f):
@@ -126,6 +140,9 @@ def main():
             row[d + "_fused"]["TFLOP/s"] = round(
                 row[d + "_flops"] / ms / 1e9, 2)
             row[d + "_vs_sdpa"] = round(row[d + "_sdpa"]["ms"] / ms, 3)
+            if both:
+                row[d + "_flash_vs_fused"] = round(
+                    ms / row[d + "_flash"]["ms"], 3)
         print(json.dumps(row), flush=True)
         results.append(row)
     if args.out:

@@ -107,6 +107,9 @@ std::vector<at::Tensor> se_wgrad(at::Tensor s, at::Tensor z, at::Tensor dl,
 std::vector<at::Tensor> attn_fwd(at::Tensor qkv, double scale);
 at::Tensor attn_bwd(at::Tensor qkv, at::Tensor o, at::Tensor lse,
                     at::Tensor dout, double scale);
+std::vector<at::Tensor> flash_attn_fwd(at::Tensor qkv, double scale);
+at::Tensor flash_attn_bwd(at::Tensor qkv, at::Tensor lse, at::Tensor dout,
+                          double scale);
 
 std::vector<at::Tensor> maxpool_fwd(at::Tensor x, long kernel, long stride,
                                     long pad);
@@ -193,6 +196,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("se_wgrad", &se_wgrad);
   m.def("attn_fwd", &attn_fwd);
   m.def("attn_bwd", &attn_bwd);
+  m.def("flash_attn_fwd", &flash_attn_fwd);
+  m.def("flash_attn_bwd", &flash_attn_bwd);
   m.def("maxpool_fwd", &maxpool_fwd);
   m.def("maxpool_bwd", &maxpool_bwd);
   m.def("global_avg_pool", &global_avg_pool);

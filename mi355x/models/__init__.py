@@ -1,7 +1,7 @@
 from .mobilenet import MobileNet, mobilenet  # noqa: F401
 from .net import Net  # noqa: F401
 from .resnet import ResNet, resnet18, resnet50  # noqa: F401
-from .vit import ViT, vit_cifar, vit_cifar_s  # noqa: F401
+from .vit import ViT, vit_cifar, vit_cifar_s, vit_s8  # noqa: F401
 
 
 def build_model(name: str, num_classes: int = 10):
@@ -38,4 +38,6 @@ def build_model(name: str, num_classes: int = 10):
         return vit_cifar(num_classes=num_classes, mlp_act="gelu")
     if name == "vit_cifar_s_gelu":
         return vit_cifar_s(num_classes=num_classes, mlp_act="gelu")
+    if name == "vit_s8":
+        return vit_s8(num_classes=num_classes)
     raise ValueError(f"unknown model {name!r}")

@@ -188,8 +188,10 @@ class LayerNorm(nn.Module):
 
 
 class MultiHeadAttention(nn.Module):
-    """Self-attention over [B,S,dim]: qkv projection, ops.attention on its
-    packed output (no permute or split in between), output projection."""
+    """Self-attention over [B,S,dim]: qkv projection, fused attention on its
+    packed output (no permute or split in between), output projection. Up to
+    256 tokens that is ops.attention (a whole head resident on the chip),
+    above it ops.flash_attention (keys streamed), up to 4096 tokens."""
 
     def __init__(self, dim, num_heads):
         super().__init__()
@@ -203,7 +205,8 @@ class MultiHeadAttention(nn.Module):
     def forward(self, x):
         B, S, D = x.shape
         qkv = self.qkv(x.reshape(B * S, D)).reshape(B, S, 3 * D)
-        o = ops.attention(qkv, self.num_heads)
+        attn = ops.attention if S <= 256 else ops.flash_attention
+        o = attn(qkv, self.num_heads)
         return self.proj(o.reshape(B * S, D)).reshape(B, S, D)
 
 

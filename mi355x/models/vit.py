@@ -1,5 +1,5 @@
-"""Vision Transformer (Dosovitskiy et al. 2021) for 32-pixel input on the
-mi355x op layer.
+"""Vision Transformer (Dosovitskiy et al. 2021) on the mi355x op layer, for
+32-pixel input (vit_cifar*) and for 224-pixel input (vit_s8).
 
 Patches are cut from the NHWC tensor by a view and one permute copy and
 embedded by a Linear(patch*patch*3, dim); a learned position embedding
@@ -24,12 +24,14 @@ the previous block's MLP output, norm2 adds the attention output, the next
 block's norm1 adds the MLP output and the final LayerNorm adds the last
 one. That is 2*depth + 1 LayerNorm launches, 2*depth of them with an add;
 only the position add is a plain tensor add. dim is a multiple of 32 up to
-4096; attention is the fused kernel of csrc/attn.hip (dim / heads must be
-32 or 64, at most 256 tokens).
+4096; dim / heads must be 32 or 64. Attention is the resident kernel of
+csrc/attn.hip up to 256 tokens and the streaming kernels of
+csrc/attn_flash.hip above that, up to 4096 tokens (a 64x64 grid).
 
 vit_cifar is dim 256, 4 heads, MLP 1024; vit_cifar_s is dim 384, 6 heads,
 MLP 1536. Both have depth 6 and 4-pixel patches; the _gelu names are the same
-shapes with mlp_act="gelu".
+shapes with mlp_act="gelu". vit_s8 is ViT-S/8 for 224-pixel input: dim 384,
+6 heads, MLP 1536 with GELU, depth 12, 8-pixel patches, 784 tokens.
 """
 
 from __future__ import annotations
@@ -113,3 +115,8 @@ def vit_cifar(num_classes=10, mlp_act="relu"):
 def vit_cifar_s(num_classes=10, mlp_act="relu"):
     return ViT(dim=384, heads=6, mlp_dim=1536, num_classes=num_classes,
                mlp_act=mlp_act)
+
+
+def vit_s8(num_classes=1000):
+    return ViT(image=224, patch=8, dim=384, depth=12, heads=6, mlp_dim=1536,
+               num_classes=num_classes, mlp_act="gelu")

@@ -945,13 +945,14 @@ def squeeze_excite(x, w1, b1, w2, b2, residual=None, act=None):
 
 
 # ---------------------------------------------------------------------------
-# multi-head self-attention (fused, S <= 256)
+# multi-head self-attention (fused: resident for S <= 256, streaming to 4096)
 # ---------------------------------------------------------------------------
 
 
-def _check_attention(qkv, num_heads, scale):
-    """The attention domain (the same on both devices): every value outside
-    it is named in a ValueError. Returns (B, S, H, dh, scale)."""
+def _check_attention(qkv, num_heads, scale, max_s=256):
+    """The attention domain (the same on both devices, and the same for
+    attention and flash_attention but for max_s): every value outside it is
+    named in a ValueError. Returns (B, S, H, dh, scale)."""
     H = num_heads
     if not isinstance(H, int) or H < 1:
         raise ValueError(f"attention: num_heads={H!r} must be a positive "
@@ -972,9 +973,9 @@ def _check_attention(qkv, num_heads, scale):
     B, S = qkv.shape[0], qkv.shape[1]
     if dh not in (32, 64):
         raise ValueError(f"attention: head width={dh} must be 32 or 64")
-    if not 1 <= S <= 256:
+    if not 1 <= S <= max_s:
         raise ValueError(f"attention: sequence length={S} must be in "
-                         "[1, 256]")
+                         f"[1, {max_s}]")
     if B < 1:
         raise ValueError(f"attention: batch={B} must be at least 1")
     scale = dh ** -0.5 if scale is None else float(scale)
@@ -984,15 +985,27 @@ def _check_attention(qkv, num_heads, scale):
     return B, S, H, dh, scale
 
 
+def _attention_cpu(qkv, scale):
+    """The fp32 formula on the CPU, qkv [B,S,3,H,dh] -> [B,S,H*dh]."""
+    B, S, _, H, dh = qkv.shape
+    q, k, v = (qkv[:, :, i].permute(0, 2, 1, 3).float() for i in range(3))
+    p = torch.softmax(scale * (q @ k.transpose(-1, -2)), dim=-1)
+    return (p @ v).permute(0, 2, 1, 3).reshape(B, S, H * dh)
+
+
+def _check_attention_dtype(qkv):
+    if qkv.dtype not in (torch.bfloat16, torch.float16):
+        raise ValueError(f"attention: the GPU kernels take bfloat16 or "
+                         f"float16, got {qkv.dtype}")
+
+
 class _AttnFn(torch.autograd.Function):
     """Fused attention over the packed qkv [B,S,3,H,dh]: the two bindings
     of csrc/attn.hip. Only o and the fp32 row log-sum-exp are kept."""
 
     @staticmethod
     def forward(ctx, qkv, scale):
-        if qkv.dtype not in (torch.bfloat16, torch.float16):
-            raise ValueError(f"attention: the GPU kernels take bfloat16 or "
-                             f"float16, got {qkv.dtype}")
+        _check_attention_dtype(qkv)
         qkv = qkv.contiguous()
         o, lse = ext().attn_fwd(qkv, scale)
         ctx.save_for_backward(qkv, o, lse)
@@ -1020,9 +1033,44 @@ def attention(qkv, num_heads, scale=None):
     qkv = qkv.reshape(B, S, 3, H, dh)
     if qkv.is_cuda:
         return _AttnFn.apply(qkv, scale)
-    q, k, v = (qkv[:, :, i].permute(0, 2, 1, 3).float() for i in range(3))
-    p = torch.softmax(scale * (q @ k.transpose(-1, -2)), dim=-1)
-    return (p @ v).permute(0, 2, 1, 3).reshape(B, S, H * dh)
+    return _attention_cpu(qkv, scale)
+
+
+class _FlashAttnFn(torch.autograd.Function):
+    """Streaming attention over the packed qkv [B,S,3,H,dh]: the two
+    bindings of csrc/attn_flash.hip. Only the fp32 row log-sum-exp is kept
+    besides qkv (the backward recomputes D from P and dP, not from o)."""
+
+    @staticmethod
+    def forward(ctx, qkv, scale):
+        _check_attention_dtype(qkv)
+        qkv = qkv.contiguous()
+        o, lse = ext().flash_attn_fwd(qkv, scale)
+        ctx.save_for_backward(qkv, lse)
+        ctx.scale = scale
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        qkv, lse = ctx.saved_tensors
+        return ext().flash_attn_bwd(qkv, lse, do.contiguous(), ctx.scale), None
+
+
+def flash_attention(qkv, num_heads, scale=None):
+    """ops.attention for sequence lengths up to 4096: the same formula,
+    layouts ([B,S,3*D] or [B,S,3,H,dh] in, [B,S,D] out), default scale and
+    errors, with the domain dh 32 or 64, 1 <= S <= 4096, scale positive. No
+    mask, no dropout. GPU: the streaming online-softmax kernels of
+    csrc/attn_flash.hip on 16-bit input at every S of the domain (never
+    eager torch, never the resident kernels: layers.MultiHeadAttention is
+    where the two ops are chosen between); K and V stream through LDS in
+    tiles, scores and probabilities stay on the chip, and the only scratch
+    in HBM is one fp32 per (batch, head, token)."""
+    B, S, H, dh, scale = _check_attention(qkv, num_heads, scale, max_s=4096)
+    qkv = qkv.reshape(B, S, 3, H, dh)
+    if qkv.is_cuda:
+        return _FlashAttnFn.apply(qkv, scale)
+    return _attention_cpu(qkv, scale)
 
 
 # ---------------------------------------------------------------------------

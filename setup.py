@@ -30,6 +30,7 @@ SRC = [
     "mi355x/csrc/ln.hip",
     "mi355x/csrc/se.hip",
     "mi355x/csrc/attn.hip",
+    "mi355x/csrc/attn_flash.hip",
     "mi355x/csrc/pool.hip",
     "mi355x/csrc/gemm.hip",
     "mi355x/csrc/gemm_mfma.hip",
