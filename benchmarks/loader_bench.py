@@ -19,9 +19,14 @@ the same process so run-to-run spread is visible next to the difference:
       cifar_example.py (zero_grad, forward, cross_entropy, backward, SGD
       step, loss.item()), host clock around a device synchronise
 
+  (r) with --resize SIZE, and instead of the above: building a batch with a
+      random resized crop to SIZE x SIZE, the resampling kernel against the
+      same batch from eager torch ops and against a fill of the output
+
 Prints one JSON line per measurement. Needs a GPU; there is no CPU fallback.
 
     python benchmarks/loader_bench.py --batches 8192,256 --reps 3
+    python benchmarks/loader_bench.py --batches 64,256 --reps 5 --resize 224
 """
 
 import argparse
@@ -139,12 +144,86 @@ def train(ds, batch, dev, reps, kinds):
                  img_per_s=round(len(ds) / s))
 
 
+def resized(ds, batch, dev, reps, size, calls=20):
+    """Random resized crop + flip to size x size, arms interleaved per rep:
+      op          ops.gather_augment(size=, scale=): one kernel
+      op_rows<R>  the same kernel with R output rows per block
+      eager       the same batch from torch ops: index gather, per-sample
+                  F.interpolate of the crop (every box differs), flip,
+                  normalize, NHWC in the compute dtype; the boxes are drawn
+                  on the host outside the timed window
+      fill        x.fill_(): the floor of writing the output once
+    """
+    import torch.nn.functional as F
+
+    from mi355x.data import rrc_params
+    from mi355x.ops.functional import _rrc_settings, compute_dtype, ext
+
+    dl = DeviceLoader(ds, batch_size=batch, device=dev)
+    g = torch.Generator().manual_seed(0)
+    idx64 = torch.randperm(len(ds), generator=g)[:batch]
+    idx = idx64.to(torch.int32).to(dev)
+    idx64 = idx64.to(dev)
+    H, W, C = dl.data_u8.shape[1:]
+    scale, ratio = (0.08, 1.0), (3 / 4, 4 / 3)
+    box = [t.tolist() for t in rrc_params(0, 1, idx64.cpu(), H, W, scale,
+                                          ratio)]
+    lo_q, hi_q, table = _rrc_settings(scale, ratio, dev)
+    like = torch.empty(0, dtype=compute_dtype(), device=dev)
+    out = torch.empty((batch, size, size, C), dtype=compute_dtype(),
+                      device=dev)
+
+    def op():
+        return ops.gather_augment(dl.data_u8, dl.targets, idx, dl.scale,
+                                  dl.shift, flip=True, epoch=1, size=size,
+                                  scale=scale, ratio=ratio)[0]
+
+    def op_rows(r):
+        return lambda: ext().gather_resize(
+            dl.data_u8, dl.targets, idx, dl.scale, dl.shift, size, size, True,
+            lo_q, hi_q, table, True, 0, 1, r, like)[0]
+
+    def eager():
+        raw = dl.data_u8[idx64].permute(0, 3, 1, 2).float()
+        rows = []
+        for b, (y0, x0, ch, cw, f) in enumerate(zip(*box)):
+            v = F.interpolate(raw[b:b + 1, :, y0:y0 + ch, x0:x0 + cw],
+                              size=(size, size), mode="bilinear",
+                              align_corners=False)
+            rows.append(v.flip(3) if f else v)
+        v = torch.cat(rows).permute(0, 2, 3, 1) * dl.scale + dl.shift
+        return v.to(compute_dtype()).contiguous()
+
+    arms = {"op": op, "eager": eager, "fill": lambda: out.fill_(0.5)}
+    arms.update({f"op_rows{r}": op_rows(r) for r in (4, 8, 32, 64)})
+    err = (op().float() - eager().float()).abs().max().item()
+    emit(what="resized_check", batch=batch, size=size,
+         max_abs_diff_op_vs_eager=err)
+    for fn in arms.values():
+        for _ in range(3):
+            fn()
+    for rep in range(reps):
+        for name, fn in arms.items():
+            e0, e1 = (torch.cuda.Event(enable_timing=True) for _ in range(2))
+            e0.record()
+            for _ in range(calls):
+                fn()
+            e1.record()
+            e1.synchronize()
+            us = e0.elapsed_time(e1) * 1e3 / calls
+            emit(what="resized", batch=batch, size=size, arm=name, rep=rep,
+                 us_per_call=round(us, 2),
+                 out_gb_per_s=round(out.numel() * 2 / us / 1e3, 1))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=50000)
     ap.add_argument("--batches", default="8192,256")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--skip-train", action="store_true")
+    ap.add_argument("--resize", type=int, default=0,
+                    help="run only the resized-loader arms, to this size")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("loader_bench.py measures on a GPU; none found")
@@ -153,6 +232,9 @@ def main():
     ds = SyntheticImageDataset(args.n, seed=1)
     kinds = ("host", "device", "device+aug")
     for batch in (int(b) for b in args.batches.split(",")):
+        if args.resize:
+            resized(ds, batch, dev, args.reps, args.resize)
+            continue
         kernel_alone(ds, batch, dev, args.reps)
         loader_only(ds, batch, dev, args.reps, kinds)
         if not args.skip_train:

@@ -20,6 +20,16 @@ Env overrides (benchmark configs; CLI shape unchanged):
                                             (DeviceLoader) for train and test
   MI355X_AUGMENT=1                          pad-4 random crop + flip on the
                                             train loader (needs DEVICE_DATA)
+  MI355X_SIZE=<pixels>                      output side of the train and test
+                                            loaders, resampled bilinearly on
+                                            the device (needs DEVICE_DATA;
+                                            e.g. 224 for MI355X_MODEL=vit_s8).
+                                            With MI355X_AUGMENT=1 the train
+                                            crop becomes a random resized crop
+                                            + flip; without it the train
+                                            loader only resizes
+  MI355X_RRC_MIN=<fraction>                 lower area bound of that random
+                                            resized crop (default 0.08)
   MI355X_CLIP_NORM=<float>                  global-norm gradient clipping in
                                             the fused step (unset or 0 = off)
   MI355X_FP16=1 MI355X_DEVICE_SCALER=1      fp16 compute with
@@ -104,20 +114,32 @@ def main():
         # batch builds it (gather + crop/flip + normalize + NHWC 16-bit)
         crop = os.environ.get("MI355X_AUGMENT", "0") == "1"
         augment = None
-        if crop or cutmix + mixup > 0:
-            # cutmix/mixup alone mix uncropped, unflipped samples
-            try:
+        try:
+            size = int(os.environ["MI355X_SIZE"]) \
+                if "MI355X_SIZE" in os.environ else None
+            if size is not None and crop:
+                # random resized crop + flip to MI355X_SIZE; cutmix/mixup
+                # with it are refused by Augment
+                augment = Augment(
+                    flip=True, cutmix=cutmix, mixup=mixup,
+                    scale=(float(os.environ.get("MI355X_RRC_MIN", "0.08")),
+                           1.0))
+            elif crop or cutmix + mixup > 0:
+                # cutmix/mixup alone mix uncropped, unflipped samples
                 augment = Augment(pad=4 if crop else 0, flip=crop,
                                   cutmix=cutmix, mixup=mixup)
-            except ValueError as e:
-                raise SystemExit(str(e))
-        trainloader = DeviceLoader(trainset, batch_size=batch, shuffle=True,
-                                   device=device, augment=augment)
-        testloader = DeviceLoader(testset, batch_size=batch, shuffle=False,
-                                  device=device)
+            trainloader = DeviceLoader(trainset, batch_size=batch,
+                                       shuffle=True, device=device,
+                                       augment=augment, size=size)
+            testloader = DeviceLoader(testset, batch_size=batch,
+                                      shuffle=False, device=device, size=size)
+        except ValueError as e:
+            raise SystemExit(str(e))
     else:
         if os.environ.get("MI355X_AUGMENT", "0") == "1":
             raise SystemExit("MI355X_AUGMENT=1 needs MI355X_DEVICE_DATA=1")
+        if "MI355X_SIZE" in os.environ:
+            raise SystemExit("MI355X_SIZE needs MI355X_DEVICE_DATA=1")
         for knob, p in (("MI355X_CUTMIX", cutmix), ("MI355X_MIXUP", mixup)):
             if p > 0:
                 raise SystemExit(f"{knob}={p:g} needs MI355X_DEVICE_DATA=1")

@@ -23,7 +23,11 @@ MI355X_SYNC_BN=1, MI355X_FP16=1 (fp16 compute + dynamic loss scaling),
 MI355X_CKPT (checkpoint path, default ./cifar_net.pth),
 MI355X_DEVICE_DATA=1 (device-resident dataset for train and test),
 MI355X_AUGMENT=1 (pad-4 random crop + flip on the train loader; needs
-MI355X_DEVICE_DATA), MI355X_CLIP_NORM=<float> (global-norm gradient
+MI355X_DEVICE_DATA), MI355X_SIZE=<pixels> (output side of the train and test
+loaders, resampled bilinearly on the device; needs MI355X_DEVICE_DATA; with
+MI355X_AUGMENT=1 the train crop becomes a random resized crop + flip whose
+lower area bound is MI355X_RRC_MIN=<fraction>, default 0.08; without it the
+train loader only resizes), MI355X_CLIP_NORM=<float> (global-norm gradient
 clipping in the fused step; unset or 0 = off), MI355X_DEVICE_SCALER=1
 (with MI355X_FP16=1: amp.DeviceGradScaler, loss scaling without a host
 sync per step), MI355X_OPTIM=sgd|lars|adamw|lamb (default sgd; lars is
@@ -113,21 +117,34 @@ def main(args):
         # epoch, so a sample augments the same on every rank.
         crop = os.environ.get("MI355X_AUGMENT", "0") == "1"
         augment = None
-        if crop or cutmix + mixup > 0:
-            # cutmix/mixup alone mix uncropped, unflipped samples
-            try:
+        try:
+            size = int(os.environ["MI355X_SIZE"]) \
+                if "MI355X_SIZE" in os.environ else None
+            if size is not None and crop:
+                # random resized crop + flip to MI355X_SIZE; cutmix/mixup
+                # with it are refused by Augment
+                augment = Augment(
+                    flip=True, cutmix=cutmix, mixup=mixup,
+                    scale=(float(os.environ.get("MI355X_RRC_MIN", "0.08")),
+                           1.0))
+            elif crop or cutmix + mixup > 0:
+                # cutmix/mixup alone mix uncropped, unflipped samples
                 augment = Augment(pad=4 if crop else 0, flip=crop,
                                   cutmix=cutmix, mixup=mixup)
-            except ValueError as e:
-                raise SystemExit(str(e))
-        trainloader = DeviceLoader(trainset, batch_size=batch,
-                                   sampler=sampler_train,
-                                   device=dev_for_loader, augment=augment)
-        testloader = DeviceLoader(testset, batch_size=batch,
-                                  sampler=sampler_test, device=dev_for_loader)
+            trainloader = DeviceLoader(trainset, batch_size=batch,
+                                       sampler=sampler_train,
+                                       device=dev_for_loader, augment=augment,
+                                       size=size)
+            testloader = DeviceLoader(testset, batch_size=batch,
+                                      sampler=sampler_test,
+                                      device=dev_for_loader, size=size)
+        except ValueError as e:
+            raise SystemExit(str(e))
     else:
         if os.environ.get("MI355X_AUGMENT", "0") == "1":
             raise SystemExit("MI355X_AUGMENT=1 needs MI355X_DEVICE_DATA=1")
+        if "MI355X_SIZE" in os.environ:
+            raise SystemExit("MI355X_SIZE needs MI355X_DEVICE_DATA=1")
         for knob, p in (("MI355X_CUTMIX", cutmix), ("MI355X_MIXUP", mixup)):
             if p > 0:
                 raise SystemExit(f"{knob}={p:g} needs MI355X_DEVICE_DATA=1")

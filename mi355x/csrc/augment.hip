@@ -385,6 +385,288 @@ __global__ __launch_bounds__(256) void gather_mix_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------
+// Random resized crop + bilinear resize: the resampling batch builder
+// ---------------------------------------------------------------------------
+// One source sample now feeds an output many times its size (3 KB -> 300 KB
+// for 32x32x3 -> 224x224x3), so the work is split the other way round from
+// the kernels above: a 256-thread block owns one sample and a band of R
+// output rows (grid = bands x B), stages the source rows the band needs in
+// LDS once, and everything a lane would otherwise recompute per element is
+// done once per block (draws, crop box, column map) or once per output row
+// (row map). The arithmetic is integer up to the normalize, so
+// mi355x.data.rrc_params and the CPU op are bit-equal twins.
+//
+//   1. thread 0: draws -> crop box (y0,x0,ch,cw,flip), first source row and
+//      row count of the band, into LDS
+//   2. column map (one packed word per output column: source element
+//      offset, whether a right neighbour exists, fx; mirrored for a flipped
+//      sample), row map (one word per output row of the band), and the
+//      source rows as 16-byte global loads of the aligned byte range that
+//      holds them
+//   3. per output row, one wave blends its two source rows into a row of
+//      cw*C uint16 (raw*wy <= 255*256)
+//   4. a lane builds 8 consecutive output elements from two LDS values each
+//      and stores 16 bytes. The band is walked as one flat element range in
+//      16-byte-aligned chunks, so a row length that is no multiple of 8 only
+//      costs element stores in the band's first and last chunk.
+//
+// wx*(r00*wy0 + r10*wy1) + wx1*(r01*wy0 + r11*wy1) is the four-tap sum of
+// the semantics, integer for integer. No division and no hash in 3 or 4.
+//
+// LDS (dynamic, see ResizeLds): staged rows + R blended rows + maps. The
+// host halves R from 16 until that is at most 20 KB, which keeps 8 blocks
+// (the 32-wave limit) on a CU's 160 KB; a wide source (W*C up to 8192
+// bytes) ends at R = 1 and up to 56 KB, 2 blocks per CU. 32x32x3 -> 224
+// takes 4.5 KB at R = 16; 48 VGPRs at most, no scratch, 8 waves per SIMD.
+// Times, the band heights tried and the write floor:
+// profiles/r22_resized_loader.md.
+
+struct Box {
+  int y0, x0, ch, cw;
+  bool f;
+};
+
+// the crop box and flip of dataset sample i; the whole image when !rrc
+DEV_INLINE Box rrc_draw(unsigned i, unsigned key, int H, int W, bool rrc,
+                        int lo_q, int hi_q, const int* __restrict__ ratio_q16,
+                        bool flip) {
+  Box b;
+  b.y0 = b.x0 = 0;
+  b.ch = H;
+  b.cw = W;
+  b.f = false;
+  if (!rrc) return b;
+  const unsigned h = mix32(i ^ key);
+  const unsigned h2 = mix32(h + 0x9E3779B9u);
+  const unsigned h3 = mix32(h2 + 0x9E3779B9u);
+  const unsigned h4 = mix32(h3 + 0x9E3779B9u);
+  const unsigned h5 = mix32(h4 + 0x9E3779B9u);
+  const unsigned h6 = mix32(h5 + 0x9E3779B9u);
+  b.f = flip && (h2 & 1u);
+  // area in Q16 of the image, then one log-uniform aspect ratio from the
+  // host's table: one draw, clamped (no retries)
+  const long aq =
+      lo_q + (long)(((h5 & 0xffffu) * (unsigned)(hi_q - lo_q + 1)) >> 16);
+  const long A = max(1l, ((long)H * W * aq) >> 16);
+  const long rq = ratio_q16[h5 >> 24];
+  b.cw = (int)min(max(isqrt_l((A * rq) >> 16), 1l), (long)W);
+  b.ch = (int)min(max(isqrt_l((A << 16) / rq), 1l), (long)H);
+  b.y0 = (int)(((h6 & 0xffffu) * (unsigned)(H - b.ch + 1)) >> 16);
+  b.x0 = (int)(((h6 >> 16) * (unsigned)(W - b.cw + 1)) >> 16);
+  return b;
+}
+
+// Q16 source coordinate of output pixel o (pixel centres, edges replicated)
+DEV_INLINE int src_q16(int o, int n_src, int n_out) {
+  const long s = ((long)(2 * o + 1) * n_src * 32768) / n_out - 32768;
+  return (int)min(max(s, 0l), (long)(n_src - 1) << 16);
+}
+
+// Rows of source a band of R output rows can touch, for any crop height up
+// to H: the band's first and last source row differ by at most
+// ceil((R-1)*ch/OH), and one more row below the last is its second tap.
+__host__ __device__ inline int resize_cap_rows(int R, int H, int OH) {
+  const long c = ((long)(R - 1) * H) / OH + 3;
+  return (int)(c < H ? c : H);
+}
+
+// byte offsets of the kernel's LDS sections; the host sizes the launch
+// from the same struct
+struct ResizeLds {
+  int stage, blend, colmap, rowmap, prm, total, bstride;
+  __host__ __device__ ResizeLds(int R, int cap_rows, int WC, int OW) {
+    stage = 0;
+    // up to 15 bytes in front of the rows (16-byte aligned loads), whole
+    // 16-byte chunks
+    blend = (15 + cap_rows * WC + 15) & ~15;
+    bstride = (WC + 1) & ~1;  // uint16 elements per blended row
+    colmap = blend + R * bstride * 2;
+    rowmap = colmap + OW * 4;
+    prm = rowmap + R * 4;
+    total = prm + 32;
+  }
+};
+
+constexpr int kResizeLdsTarget = 20 * 1024;  // 8 blocks on a 160 KB CU
+constexpr int kResizeLdsMax = 64 * 1024;
+
+// one output element from its blended row
+template <typename T16, int C>
+DEV_INLINE short resize_pix(const unsigned short* __restrict__ bl,
+                            unsigned cm, int c, float s, float t) {
+  const int e0 = (int)(cm & 0x3fffu) + c;
+  const int e1 = e0 + ((cm >> 14) & 1u ? C : 0);
+  const int fx = (int)(cm >> 16);
+  const int val = (int)bl[e0] * (256 - fx) + (int)bl[e1] * fx;
+  // at most 255 * 2^16: exact in fp32, and so is the 2^-16
+  const float v = (float)val * (1.f / 65536.f);
+  // not contracted (pragma above): the CPU path's mul-then-add
+  const float p = v * s;
+  return f32_to_s16<T16>(p + t);
+}
+
+template <typename T16, int C>
+__global__ __launch_bounds__(256) void gather_resize_kernel(
+    const unsigned char* __restrict__ data, const long* __restrict__ targets,
+    const int* __restrict__ indices, const float* __restrict__ scale,
+    const float* __restrict__ shift, const int* __restrict__ ratio_q16,
+    T16* __restrict__ x, long* __restrict__ y, int N, int H, int W, int OH,
+    int OW, int R, int cap_rows, bool rrc, int lo_q, int hi_q, bool flip,
+    unsigned key) {
+  extern __shared__ __align__(16) unsigned char lds[];
+  const int WC = W * C, OWC = OW * C;
+  const ResizeLds L(R, cap_rows, WC, OW);
+  unsigned char* stage = lds + L.stage;
+  unsigned short* blend = reinterpret_cast<unsigned short*>(lds + L.blend);
+  unsigned* colmap = reinterpret_cast<unsigned*>(lds + L.colmap);
+  unsigned* rowmap = reinterpret_cast<unsigned*>(lds + L.rowmap);
+  int* prm = reinterpret_cast<int*>(lds + L.prm);
+
+  const int tid = threadIdx.x, b = blockIdx.y, oy0 = blockIdx.x * R;
+  const int rows = min(R, OH - oy0);
+  const int i = indices[b];
+  // an index outside the dataset reads nothing: label -1, raw 0 everywhere
+  const bool ok = (unsigned)i < (unsigned)N;
+
+  if (tid == 0) {
+    const Box bx =
+        rrc_draw((unsigned)i, key, H, W, rrc, lo_q, hi_q, ratio_q16, flip);
+    const int iy_first = src_q16(oy0, bx.ch, OH) >> 16;
+    const int iy_last = src_q16(oy0 + rows - 1, bx.ch, OH) >> 16;
+    prm[0] = bx.y0;
+    prm[1] = bx.x0;
+    prm[2] = bx.ch;
+    prm[3] = bx.cw;
+    prm[4] = bx.f;
+    prm[5] = iy_first;
+    // never more than the launch reserved (resize_cap_rows is the bound)
+    prm[6] = min(min(iy_last + 1, bx.ch - 1) - iy_first + 1, cap_rows);
+    if (blockIdx.x == 0) y[b] = ok ? targets[i] : -1;
+  }
+  __syncthreads();
+  const int y0 = prm[0], x0 = prm[1], ch = prm[2], cw = prm[3];
+  const bool f = prm[4] != 0;
+  const int iy_first = prm[5], nsrc = prm[6];
+
+  for (int ox = tid; ox < OW; ox += 256) {
+    const int sx = src_q16(f ? OW - 1 - ox : ox, cw, OW);
+    const int ix = sx >> 16, fx = (sx >> 8) & 255;
+    colmap[ox] = (unsigned)(ix * C) | (ix + 1 < cw ? 1u << 14 : 0u) |
+                 (unsigned)fx << 16;
+  }
+  if (tid < rows) {
+    const int sy = src_q16(oy0 + tid, ch, OH);
+    const int iy = sy >> 16, fy = (sy >> 8) & 255;
+    const int r0 = min(iy - iy_first, nsrc - 1);
+    const int r1 = min(min(iy + 1, ch - 1) - iy_first, nsrc - 1);
+    rowmap[tid] = (unsigned)r0 | (unsigned)(r1 - r0) << 13 | (unsigned)fy << 16;
+  }
+  // Source rows y0+iy_first .. +nsrc-1, whole rows: one contiguous byte
+  // range of the sample. It is loaded as the 16-byte-aligned chunks that
+  // cover it; a chunk that sticks out of the dataset (possible only at its
+  // two ends) is read byte by byte, inside bytes only.
+  const long s_off = ((long)(ok ? i : 0) * H + y0 + iy_first) * WC;
+  const int head = (int)(reinterpret_cast<uintptr_t>(data + s_off) & 15);
+  if (ok) {
+    const unsigned char* abase = data + s_off - head;
+    const unsigned char* dend = data + (long)N * H * WC;
+    const int nchunk = (head + nsrc * WC + 15) >> 4;
+    for (int k = tid; k < nchunk; k += 256) {
+      const unsigned char* p = abase + 16 * k;
+      if (p >= data && p + 16 <= dend) {
+        *reinterpret_cast<int4v*>(stage + 16 * k) =
+            *reinterpret_cast<const int4v*>(p);
+      } else {
+#pragma unroll 1
+        for (int u = 0; u < 16; ++u)
+          stage[16 * k + u] = (p + u >= data && p + u < dend) ? p[u] : 0;
+      }
+    }
+  }
+  __syncthreads();
+
+  // one wave per output row: the two source rows, weighted, as uint16
+  const int cwC = cw * C;
+  for (int j = tid >> 6; j < rows; j += 4) {
+    const unsigned rm = rowmap[j];
+    const int fy = (int)(rm >> 16);
+    const unsigned char* s0 = stage + head + (int)(rm & 0x1fffu) * WC + x0 * C;
+    const unsigned char* s1 = s0 + ((rm >> 13) & 1u ? WC : 0);
+    unsigned short* bl = blend + j * L.bstride;
+    for (int e = tid & 63; e < cwC; e += 64)
+      bl[e] = ok ? (unsigned short)(s0[e] * (256 - fy) + s1[e] * fy) : 0;
+  }
+  __syncthreads();
+
+  float sc[4], sf[4];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    sc[c] = c < C ? scale[c] : 0.f;
+    sf[c] = c < C ? shift[c] : 0.f;
+  }
+
+  // The band's elements are one flat range of x. Chunk q is the 8 elements
+  // at the 16-byte-aligned address xa + 8q; rel is its first element
+  // relative to the band (negative in chunk 0 if the band starts inside a
+  // chunk), (j, m) the row and the position in the row of that element,
+  // stepped by 2048 elements per round without a division.
+  const long band0 = ((long)b * OH + oy0) * OWC;
+  const int ohead = (int)(band0 & 7);
+  short* xa = reinterpret_cast<short*>(x) + (band0 - ohead);
+  const int total = rows * OWC;
+  const int nq = (ohead + total + 7) >> 3;
+  const int step_j = 2048 / OWC, step_m = 2048 - step_j * OWC;
+  int rel = 8 * tid - ohead;
+  int j = rel >= 0 ? rel / OWC : -((-rel + OWC - 1) / OWC);
+  int m = rel - j * OWC;
+  for (int q = tid; q < nq; q += 256) {
+    if (rel >= 0 && rel + 8 <= total) {
+      const unsigned short* bl = blend + j * L.bstride;
+      int ox = m / C, c = m - ox * C, mm = m;
+      short8 o;
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        // selects, not runtime-indexed arrays (those go to scratch)
+        const float s = c == 0 ? sc[0] : c == 1 ? sc[1] : c == 2 ? sc[2] : sc[3];
+        const float t = c == 0 ? sf[0] : c == 1 ? sf[1] : c == 2 ? sf[2] : sf[3];
+        o[u] = resize_pix<T16, C>(bl, colmap[ox], c, s, t);
+        if (++c == C) {
+          c = 0;
+          ++ox;
+        }
+        if (++mm == OWC) {  // next row of the band
+          mm = 0;
+          ox = 0;
+          c = 0;
+          bl += L.bstride;
+        }
+      }
+      *reinterpret_cast<short8*>(xa + 8 * q) = o;
+    } else {
+      // the band's first or last chunk: only the elements inside the band
+#pragma unroll 1
+      for (int u = 0; u < 8; ++u) {
+        const int r = rel + u;
+        if (r < 0 || r >= total) continue;
+        const int jj = r / OWC, m2 = r - jj * OWC;
+        const int ox = m2 / C, c = m2 - ox * C;
+        const float s = c == 0 ? sc[0] : c == 1 ? sc[1] : c == 2 ? sc[2] : sc[3];
+        const float t = c == 0 ? sf[0] : c == 1 ? sf[1] : c == 2 ? sf[2] : sf[3];
+        xa[8 * q + u] =
+            resize_pix<T16, C>(blend + jj * L.bstride, colmap[ox], c, s, t);
+      }
+    }
+    rel += 2048;
+    j += step_j;
+    m += step_m;
+    if (m >= OWC) {
+      m -= OWC;
+      ++j;
+    }
+  }
+}
+
 // same cap as elementwise.hip's ew_grid
 inline int aug_grid(long n, int per_thread, int block = 256) {
   long blocks = cdiv_l(n, (long)block * per_thread);
@@ -507,6 +789,104 @@ std::tuple<at::Tensor, at::Tensor> gather_augment(
                        scale.data_ptr<float>(), shift.data_ptr<float>(),
                        (T16*)x.data_ptr(), y.data_ptr<long>(), (int)N, (int)B,
                        (int)H, (int)W, (int)C, (int)pad, flip, key);
+  });
+  return {x, y};
+}
+
+// Random resized crop + bilinear resize to (OH, OW). rrc: draw a crop box
+// per sample (lo_q, hi_q: the area bounds round(scale*65536); ratio_q16:
+// the 256-entry log-uniform aspect table, int32 on the device; flip as in
+// gather_augment); without it the whole image is resized and nothing is
+// drawn. band_rows: output rows per block, 0 for the default of 16; either
+// is halved until the block's LDS is within kResizeLdsTarget.
+//
+// Domain of the LDS staging: C in 1..4, H and W at most 4096, output sides
+// in [1, 4096], W*C at most 8192 bytes (then even a one-row band, which
+// needs 3 staged rows, 1 blended row and the maps, fits 64 KB), B at most
+// 65535 (the grid's second dimension).
+std::tuple<at::Tensor, at::Tensor> gather_resize(
+    at::Tensor data_u8, at::Tensor targets, at::Tensor indices,
+    at::Tensor scale, at::Tensor shift, int64_t OH, int64_t OW, bool rrc,
+    int64_t lo_q, int64_t hi_q, c10::optional<at::Tensor> ratio_q16, bool flip,
+    int64_t seed, int64_t epoch, int64_t band_rows, at::Tensor like) {
+  CHECK_GPU(data_u8);
+  CHECK_GPU(targets);
+  CHECK_GPU(indices);
+  CHECK_GPU(scale);
+  CHECK_GPU(shift);
+  CHECK_CONTIG(data_u8);
+  CHECK_CONTIG(targets);
+  CHECK_CONTIG(indices);
+  CHECK_CONTIG(scale);
+  CHECK_CONTIG(shift);
+  CHECK_16BIT(like);
+  TORCH_CHECK(data_u8.scalar_type() == at::kByte && data_u8.dim() == 4,
+              "data_u8 must be (N,H,W,C) uint8");
+  TORCH_CHECK(targets.scalar_type() == at::kLong && targets.dim() == 1 &&
+                  targets.size(0) == data_u8.size(0),
+              "targets must be (N,) int64");
+  TORCH_CHECK(indices.scalar_type() == at::kInt && indices.dim() == 1 &&
+                  indices.size(0) >= 1,
+              "indices must be (B,) int32 with B >= 1");
+  const long N = data_u8.size(0), H = data_u8.size(1), W = data_u8.size(2),
+             C = data_u8.size(3), B = indices.size(0);
+  TORCH_CHECK(C >= 1 && C <= 4, "gather_resize supports 1..4 channels, got ",
+              C);
+  TORCH_CHECK(scale.scalar_type() == at::kFloat && scale.numel() == C &&
+                  shift.scalar_type() == at::kFloat && shift.numel() == C,
+              "scale and shift must be (C,) float32");
+  TORCH_CHECK(H >= 1 && H <= 4096 && W >= 1 && W <= 4096,
+              "gather_resize: H and W must be in [1, 4096], got ", H, " x ",
+              W);
+  TORCH_CHECK(OH >= 1 && OH <= 4096 && OW >= 1 && OW <= 4096,
+              "gather_resize: output sides must be in [1, 4096], got ", OH,
+              " x ", OW);
+  TORCH_CHECK(W * C <= 8192, "gather_resize: a source row of W*C = ", W * C,
+              " bytes does not fit the LDS staging (at most 8192)");
+  TORCH_CHECK(N >= 1 && N <= INT_MAX && B <= 65535,
+              "gather_resize: N must be in [1, 2^31) and B at most 65535, got ",
+              N, " and ", B);
+  TORCH_CHECK(band_rows >= 0 && band_rows <= 64,
+              "gather_resize: band_rows must be in [0, 64], got ", band_rows);
+  const int* ratio = nullptr;
+  if (rrc) {
+    TORCH_CHECK(lo_q >= 1 && lo_q <= hi_q && hi_q <= 65536,
+                "gather_resize: need 1 <= lo_q <= hi_q <= 65536, got ", lo_q,
+                " and ", hi_q);
+    TORCH_CHECK(ratio_q16.has_value(), "gather_resize: rrc needs ratio_q16");
+    const at::Tensor& r = *ratio_q16;
+    CHECK_GPU(r);
+    CHECK_CONTIG(r);
+    TORCH_CHECK(r.scalar_type() == at::kInt && r.numel() == 256,
+                "ratio_q16 must be 256 int32 values");
+    ratio = r.data_ptr<int>();
+  }
+  const unsigned key =
+      mix32((unsigned)(uint64_t)seed * 0x9E3779B9u + (unsigned)(uint64_t)epoch);
+
+  int R = (int)std::min<long>(band_rows ? band_rows : 16, OH);
+  auto lds_of = [&](int r) {
+    return ResizeLds(r, resize_cap_rows(r, (int)H, (int)OH), (int)(W * C),
+                     (int)OW).total;
+  };
+  while (R > 1 && lds_of(R) > kResizeLdsTarget) R = (R + 1) / 2;
+  const int lds_bytes = lds_of(R);
+  TORCH_CHECK(lds_bytes <= kResizeLdsMax, "gather_resize: ", lds_bytes,
+              " bytes of LDS for W*C = ", W * C, " and OW = ", OW);
+
+  auto x = at::empty({B, OH, OW, C}, like.options().device(data_u8.device()));
+  auto y = at::empty({B}, targets.options());
+  const dim3 grid((unsigned)cdiv_l(OH, R), (unsigned)B);
+  DISPATCH_16(like, T16, {
+    pick<1, 2, 3, 4>((int)C, [&](auto CC) {
+      launch256(gather_resize_kernel<T16, CC>, grid, (size_t)lds_bytes,
+                data_u8.data_ptr<unsigned char>(), targets.data_ptr<long>(),
+                indices.data_ptr<int>(), scale.data_ptr<float>(),
+                shift.data_ptr<float>(), ratio, (T16*)x.data_ptr(),
+                y.data_ptr<long>(), (int)N, (int)H, (int)W, (int)OH, (int)OW,
+                R, resize_cap_rows(R, (int)H, (int)OH), rrc, (int)lo_q,
+                (int)hi_q, flip, key);
+    });
   });
   return {x, y};
 }

@@ -156,6 +156,11 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> gather_augment_mix(
     at::Tensor data_u8, at::Tensor targets, at::Tensor indices,
     at::Tensor scale, at::Tensor shift, int64_t pad, bool flip, int64_t tc,
     int64_t tm, double inv_hw, int64_t seed, int64_t epoch, at::Tensor like);
+std::tuple<at::Tensor, at::Tensor> gather_resize(
+    at::Tensor data_u8, at::Tensor targets, at::Tensor indices,
+    at::Tensor scale, at::Tensor shift, int64_t OH, int64_t OW, bool rrc,
+    int64_t lo_q, int64_t hi_q, c10::optional<at::Tensor> ratio_q16, bool flip,
+    int64_t seed, int64_t epoch, int64_t band_rows, at::Tensor like);
 
 void register_rccl(py::module_& m);
 
@@ -214,4 +219,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("meter_update", &meter_update);
   m.def("gather_augment", &gather_augment);
   m.def("gather_augment_mix", &gather_augment_mix);
+  m.def("gather_resize", &gather_resize);
 }

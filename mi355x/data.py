@@ -27,6 +27,9 @@ these are mandatory, not convenience):
                          is one fused HIP kernel (gather by sampler index,
                          pad-4 random crop + flip per Augment, normalize,
                          16-bit NHWC out) — no host work or H2D per step.
+                         With size= the kernel resamples bilinearly to
+                         another size, from a random resized crop when the
+                         Augment has scale= (rrc_params).
 """
 
 from __future__ import annotations
@@ -47,6 +50,8 @@ __all__ = [
     "DataLoader",
     "augment_params",
     "mix_params",
+    "rrc_params",
+    "rrc_quantize",
     "MIX_NONE",
     "MIX_CUT",
     "MIX_UP",
@@ -517,6 +522,76 @@ def mix_params(seed: int, epoch: int, indices, H: int, W: int,
             torch.from_numpy(lam.astype(np.float32)))
 
 
+def rrc_quantize(scale, ratio):
+    """Integer form of the random-resized-crop settings: ``(lo_q, hi_q,
+    ratio_q16)``. lo_q/hi_q are the area bounds round(scale*65536);
+    ratio_q16 is the log-uniform aspect table, 256 Q16 int32 values, entry k
+    the ratio at quantile (k+0.5)/256, computed in float64. The kernel and
+    the numpy twin both take them from here, so neither evaluates a log or
+    an exp and the two cannot round differently."""
+    lo, hi = (float(v) for v in scale)
+    r0, r1 = (float(v) for v in ratio)
+    if not 0.0 < lo <= hi <= 1.0:
+        raise ValueError(
+            f"scale must satisfy 0 < scale[0] <= scale[1] <= 1, got {(lo, hi)}")
+    if not 0.0 < r0 <= r1:
+        raise ValueError(
+            f"ratio must satisfy 0 < ratio[0] <= ratio[1], got {(r0, r1)}")
+    if r0 < 2.0 ** -15 or r1 > 2.0 ** 14:  # Q16 in int32, and never 0
+        raise ValueError(f"ratio must lie in [2^-15, 2^14], got {(r0, r1)}")
+    lo_q = max(1, int(round(lo * 65536)))
+    hi_q = max(lo_q, int(round(hi * 65536)))
+    q = (np.arange(256, dtype=np.float64) + 0.5) / 256.0
+    table = np.round(65536.0 * np.exp(
+        math.log(r0) + q * (math.log(r1) - math.log(r0))))
+    return lo_q, hi_q, torch.from_numpy(table.astype(np.int32))
+
+
+def rrc_params(seed: int, epoch: int, indices, H: int, W: int, scale,
+               ratio=(3 / 4, 4 / 3)):
+    """Random-resized-crop boxes and flip bits of the samples ``indices`` in
+    ``epoch``, for H x W images: ``(y0, x0, ch, cw, flip)`` int64 tensors.
+    The box is rows [y0, y0+ch) and columns [x0, x0+cw), always inside the
+    image with ch, cw >= 1; its area is uniform in ``scale`` times H*W and
+    its aspect ratio cw/ch log-uniform in ``ratio``.
+
+    The draws continue the hash chain of the dataset index (h, h2: crop and
+    flip; h3, h4: mixing; here h5, h6), so they are the same at any batch
+    size, world size or rank; the flip is augment_params' bit. One draw,
+    clamped to the image: not torchvision's ten retries and centre-crop
+    fallback, so a box that would stick out is shortened on that side
+    instead of redrawn. All integer arithmetic: this is the CPU twin of
+    rrc_draw in csrc/augment.hip and the oracle of its tests.
+    """
+    H, W = int(H), int(W)
+    if not (1 <= H <= 4096 and 1 <= W <= 4096):
+        raise ValueError(f"rrc_params: H and W must be in [1, 4096], got "
+                         f"{H} x {W}")
+    lo_q, hi_q, table = rrc_quantize(scale, ratio)
+    i = np.asarray(torch.as_tensor(indices, dtype=torch.int64).numpy())
+    if i.size and (i.min() < 0 or i.max() > 0xFFFFFFFF):
+        raise ValueError("rrc_params: index outside uint32 range")
+    i = i.astype(np.uint64)
+    key0 = ((int(seed) & 0xFFFFFFFF) * _GOLDEN + (int(epoch) & 0xFFFFFFFF)) \
+        & 0xFFFFFFFF
+    key = _mix32(np.array(key0, dtype=np.uint64))
+    hs = [_mix32(i ^ key)]
+    for _ in range(5):
+        hs.append(_mix32((hs[-1] + np.uint64(_GOLDEN)) & _M32))
+    h2, h5, h6 = hs[1], hs[4], hs[5]
+    aq = lo_q + (((h5 & np.uint64(0xFFFF)).astype(np.int64)
+                  * (hi_q - lo_q + 1)) >> 16)
+    A = np.maximum(1, (H * W * aq) >> 16)
+    rq = table.numpy().astype(np.int64)[(h5 >> np.uint64(24)).astype(np.int64)]
+    cw = np.clip(_isqrt((A * rq) >> 16), 1, W)
+    ch = np.clip(_isqrt((A << 16) // rq), 1, H)
+    y0 = ((h6 & np.uint64(0xFFFF)).astype(np.int64) * (H - ch + 1)) >> 16
+    x0 = ((h6 >> np.uint64(16)).astype(np.int64) * (W - cw + 1)) >> 16
+    f = (h2 & np.uint64(1)).astype(np.int64)
+    return tuple(torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64))
+                 for a in (y0, x0, ch, cw, f))
+
+
 class Augment:
     """Train-time augmentation settings: zero-pad by ``pad`` and take a
     random crop of the original size, then flip horizontally with
@@ -526,10 +601,16 @@ class Augment:
     ``cutmix`` / ``mixup`` are the probabilities that a sample is mixed with
     its partner in the batch (``ops.gather_augment_mix``); they must sum to
     at most 1. With either above 0 a DeviceLoader yields ``(x, MixTarget)``
-    for ``ops.cross_entropy``; with both 0 nothing changes."""
+    for ``ops.cross_entropy``; with both 0 nothing changes.
+
+    With ``scale=(lo, hi)`` the crop is a random resized crop instead
+    (``rrc_params``: area uniform in ``scale`` of the image, aspect ratio
+    log-uniform in ``ratio``), resampled bilinearly to the loader's ``size``;
+    ``pad`` then plays no part. It does not combine with cutmix / mixup: the
+    pair kernel does not resample yet."""
 
     def __init__(self, pad: int = 4, flip: bool = True, cutmix: float = 0.0,
-                 mixup: float = 0.0):
+                 mixup: float = 0.0, scale=None, ratio=(3 / 4, 4 / 3)):
         self.pad = int(pad)
         self.flip = bool(flip)
         self.cutmix = float(cutmix)
@@ -539,12 +620,24 @@ class Augment:
             raise ValueError(
                 "cutmix and mixup must be probabilities with cutmix + mixup "
                 f"<= 1, got {self.cutmix} and {self.mixup}")
+        self.scale = None if scale is None else tuple(float(v) for v in scale)
+        self.ratio = tuple(float(v) for v in ratio)
+        if self.scale is not None:
+            rrc_quantize(self.scale, self.ratio)  # validates both
+            if self.mixes:
+                raise ValueError(
+                    f"Augment(scale={self.scale}) with cutmix={self.cutmix}, "
+                    f"mixup={self.mixup}: the pair kernel does not resample "
+                    "yet")
 
     @property
     def mixes(self) -> bool:
         return self.cutmix + self.mixup > 0
 
     def __repr__(self) -> str:
+        if self.scale is not None:
+            return (f"Augment(scale={self.scale}, ratio={self.ratio}, "
+                    f"flip={self.flip})")
         mix = (f", cutmix={self.cutmix}, mixup={self.mixup}"
                if self.mixes else "")
         return f"Augment(pad={self.pad}, flip={self.flip}{mix})"
@@ -574,13 +667,37 @@ class DeviceLoader:
     ``ops.gather_augment_mix`` instead (still one kernel) and the loader
     yields ``(x, MixTarget(y_a, y_b, lam))``; the partner of batch position
     b is position B-1-b of the same batch.
+
+    ``size`` (an int or ``(OH, OW)``) is the output size and selects the
+    resampling kernel (``ops.gather_augment(size=...)``, still one launch):
+    with ``augment=None`` the whole image is resized bilinearly (evaluation);
+    with an ``Augment(scale=...)`` each sample's random resized crop is. An
+    ``Augment(scale=...)`` without ``size`` crops and resamples back to the
+    source size. Pad-crop followed by a resize, and mixing at another size,
+    are not offered.
     """
 
     def __init__(self, dataset, batch_size: int = 1, shuffle: bool = False,
                  sampler: Optional[Sequence[int]] = None,
                  drop_last: bool = False, device=None,
                  augment: Optional[Augment] = None,
-                 mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5), seed: int = 0):
+                 mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5), seed: int = 0,
+                 size=None):
+        rrc = augment is not None and augment.scale is not None
+        if size is not None and augment is not None and augment.mixes:
+            raise ValueError(
+                f"DeviceLoader(size={size}) with {augment!r}: the pair "
+                "kernel does not resample yet")
+        if size is not None and augment is not None and not rrc:
+            raise ValueError(
+                f"DeviceLoader(size={size}) needs an Augment with scale= "
+                f"(or augment=None), got {augment!r}")
+        if size is None and rrc:
+            size = tuple(dataset.data_u8.shape[1:3])
+        if size is not None:
+            from mi355x.ops.functional import resize_arg
+            size = resize_arg(size)
+        self.size = size
         self.dataset = dataset
         self.batch_size = batch_size
         self.shuffle = shuffle
@@ -655,6 +772,15 @@ class DeviceLoader:
                     cutmix=self.augment.cutmix, mixup=self.augment.mixup,
                     seed=self.seed, epoch=aug_epoch)
                 yield x.permute(0, 3, 1, 2), ops.MixTarget(y_a, y_b, lam)
+                continue
+            if self.size is not None:
+                x, y = ops.gather_augment(
+                    self.data_u8, self.targets, idx_dev[s:e], self.scale,
+                    self.shift, flip=flip, seed=self.seed, epoch=aug_epoch,
+                    size=self.size,
+                    scale=self.augment.scale if self.augment else None,
+                    ratio=self.augment.ratio if self.augment else (1.0, 1.0))
+                yield x.permute(0, 3, 1, 2), y
                 continue
             x, y = ops.gather_augment(
                 self.data_u8, self.targets, idx_dev[s:e], self.scale,

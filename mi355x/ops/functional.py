@@ -15,6 +15,7 @@ extension (no silent PyTorch fallback on GPU).
 
 from __future__ import annotations
 
+import functools
 import math
 from typing import NamedTuple
 
@@ -1236,8 +1237,68 @@ def cross_entropy(logits, target, label_smoothing=0.0):
 # ---------------------------------------------------------------------------
 
 
-def gather_augment(data_u8, targets, indices, scale, shift, *, pad=0,
-                   flip=False, seed=0, epoch=0):
+@functools.lru_cache(maxsize=16)
+def _rrc_settings(scale, ratio, device):
+    """(lo_q, hi_q, ratio table on ``device``): built and uploaded once per
+    setting, not per batch."""
+    from mi355x.data import rrc_quantize
+
+    lo_q, hi_q, table = rrc_quantize(scale, ratio)
+    return lo_q, hi_q, table.to(device)
+
+
+def resize_arg(size):
+    """``size`` (an int or an (OH, OW) pair) as a validated (OH, OW)."""
+    oh, ow = (size, size) if isinstance(size, int) else size
+    oh, ow = int(oh), int(ow)
+    if not (1 <= oh <= 4096 and 1 <= ow <= 4096):
+        raise ValueError(f"size must have sides in [1, 4096], got {size}")
+    return oh, ow
+
+
+def _src_q16(n_out, n_src):
+    """Q16 source coordinates of n_out output pixels over n_src (B,) source
+    pixels: pixel centres, edges replicated. int64 (B, n_out)."""
+    o = torch.arange(n_out, dtype=torch.int64)[None, :]
+    n = n_src[:, None]
+    s = ((2 * o + 1) * n * 32768) // n_out - 32768
+    return torch.minimum(s.clamp_(min=0), (n - 1) << 16)
+
+
+def _gather_resize_cpu(data_u8, idx, oh, ow, scale, ratio, flip, seed, epoch):
+    """The fp32 twin of gather_resize_kernel before normalization: (B,OH,OW,C)
+    float32, each value an integer four-tap sum times 2^-16."""
+    from mi355x.data import rrc_params
+
+    N, H, W, C = data_u8.shape
+    if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= N):
+        raise IndexError(f"gather_augment: index outside dataset of {N}")
+    B = idx.numel()
+    if scale is None:
+        y0 = x0 = f = torch.zeros(B, dtype=torch.int64)
+        ch = torch.full((B,), H, dtype=torch.int64)
+        cw = torch.full((B,), W, dtype=torch.int64)
+    else:
+        y0, x0, ch, cw, f = rrc_params(seed, epoch, idx, H, W, scale, ratio)
+        if not flip:
+            f = torch.zeros_like(f)
+    sy, sx = _src_q16(oh, ch), _src_q16(ow, cw)
+    sx = torch.where(f[:, None] != 0, sx.flip(1), sx)  # column OW-1-ox
+    iy, fy = sy >> 16, (sy >> 8) & 255
+    ix, fx = sx >> 16, (sx >> 8) & 255
+    acc = torch.zeros((B, oh, ow, C), dtype=torch.int64)
+    for ty, wy in ((iy, 256 - fy), (torch.minimum(iy + 1, ch[:, None] - 1), fy)):
+        for tx, wx in ((ix, 256 - fx),
+                       (torch.minimum(ix + 1, cw[:, None] - 1), fx)):
+            raw = data_u8[idx[:, None, None], (y0[:, None] + ty)[:, :, None],
+                          (x0[:, None] + tx)[:, None, :]]
+            acc += raw.to(torch.int64) * (wy[:, :, None] * wx[:, None, :])[..., None]
+    return acc.to(torch.float32) * (1.0 / 65536.0)
+
+
+def gather_augment(data_u8, targets, indices, norm_scale, shift, *, pad=0,
+                   flip=False, seed=0, epoch=0, size=None, scale=None,
+                   ratio=(3 / 4, 4 / 3)):
     """Build a batch from the uint8 NHWC dataset: gather ``indices``,
     zero-pad by ``pad`` and crop at a random offset, flip, then
     ``v*scale[c] + shift[c]`` (a padded pixel is raw 0, so it comes out as
@@ -1253,17 +1314,53 @@ def gather_augment(data_u8, targets, indices, scale, shift, *, pad=0,
     index and returns an all-padding image with label -1 (which the
     cross-entropy kernel turns into a NaN loss). DeviceLoader checks the
     epoch's indices on the host before it launches anything.
+
+    ``size`` (an int or ``(OH, OW)``) selects the resampling builder
+    instead: x is (B,OH,OW,C) and ``pad`` plays no part. With
+    ``scale=(lo, hi)`` each sample's box is a random resized crop
+    (``mi355x.data.rrc_params``: area uniform in ``scale`` of the image,
+    aspect log-uniform in ``ratio``; one draw clamped to the image, not
+    torchvision's ten retries) and ``flip`` mirrors it; with ``scale=None``
+    the box is the whole image and nothing is flipped (evaluation). The box
+    is resampled bilinearly at pixel centres (align_corners=False, no
+    antialias, edges replicated inside the box) with 8-bit weights in
+    integer arithmetic, then normalized as above. GPU: one kernel
+    (gather_resize_kernel, source rows staged in LDS); C <= 4, H, W <= 4096
+    and W*C <= 8192 bytes, else a RuntimeError that names the value. CPU:
+    the fp32 twin, bit-equal before the rounding to 16 bits. (The normalize
+    multiplier is ``norm_scale`` here; it is passed by position.)
     """
+    if size is None:
+        if scale is not None:
+            raise ValueError(f"gather_augment: scale={scale} needs size=")
+        if data_u8.is_cuda:
+            like = torch.empty(0, dtype=compute_dtype(),
+                               device=data_u8.device)
+            x, y = ext().gather_augment(data_u8, targets, indices,
+                                        norm_scale, shift, int(pad),
+                                        bool(flip), int(seed), int(epoch),
+                                        like)
+            return x, y
+        idx = indices.to(torch.int64)
+        v = _gather_raw_cpu(data_u8, idx, pad, flip, seed, epoch,
+                            "gather_augment")
+        return v * norm_scale + shift, targets[idx]
+    oh, ow = resize_arg(size)
+    if scale is not None:
+        scale = tuple(float(v) for v in scale)
+        ratio = tuple(float(v) for v in ratio)
     if data_u8.is_cuda:
+        lo_q, hi_q, table = (0, 0, None) if scale is None else \
+            _rrc_settings(scale, ratio, data_u8.device)
         like = torch.empty(0, dtype=compute_dtype(), device=data_u8.device)
-        x, y = ext().gather_augment(data_u8, targets, indices, scale, shift,
-                                    int(pad), bool(flip), int(seed),
-                                    int(epoch), like)
-        return x, y
+        return tuple(ext().gather_resize(
+            data_u8, targets, indices, norm_scale, shift, oh, ow,
+            scale is not None, lo_q, hi_q, table, bool(flip), int(seed),
+            int(epoch), 0, like))  # 0: the default band of output rows
     idx = indices.to(torch.int64)
-    v = _gather_raw_cpu(data_u8, idx, pad, flip, seed, epoch,
-                        "gather_augment")
-    return v * scale + shift, targets[idx]
+    v = _gather_resize_cpu(data_u8, idx, oh, ow, scale, ratio, flip, seed,
+                           epoch)
+    return v * norm_scale + shift, targets[idx]
 
 
 def _gather_raw_cpu(data_u8, idx, pad, flip, seed, epoch, who):
